@@ -25,8 +25,19 @@ is split over the N ranks, n = 800/N columns each -- the reference's ``-b 800``
 run (fpcode/run.sh:39, ``in_proc = min(batch, N - start) / num_procs``,
 fpcode/neural_network.cpp:458); ``value`` is that run's images/s.  At N > 1 the
 record also carries the weak-scaling run (800 images per GPU per step, global
-batch 800*N) as the labelled secondary ``weak`` sub-record (``--secondary off``
-skips it).  ``--scaling weak`` swaps the two.  At N = 1 both are batch 800.
+batch 800*N) as the labelled secondary ``weak`` sub-record when ``--full`` is given
+(``--secondary off`` skips it even then).  ``--scaling weak`` swaps the two.  At N = 1
+both are batch 800.
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the K
+timed steps, the record.  ``--full`` adds what takes runs of its own: the secondary
+scaling sub-record and the step's all-reduce timed alone (``allreduce_us``,
+``allreduce_bytes``, ``allreduce_busbw_GBps``; ``allreduce_us`` is null without it).
+
+``--dump-outputs DIR`` writes what the last timed step left a caller of the step with,
+the parameters W1, b1, W2, b2, as ``DIR/<name>.npy`` (float64 for ``--dtype f64``, else
+float32; rank 0 writes).  Data and initial weights are seeded, so two builds run with
+the same arguments can be compared array for array.
 
 N > 1 choices made by measurement on the node, inside a wall-time budget
 (``--tune-budget-s``): the gradient all-reduce (the cost model's xGMI pick, the
@@ -62,7 +73,7 @@ def parse(argv=None):
                     help="strong (default, the metric's config): --batch is the global batch, split over the "
                          "ranks; weak: --batch images per GPU")
     ap.add_argument("--secondary", default="auto", choices=["auto", "off"],
-                    help="auto: with N > 1 also time the other scaling mode into a labelled sub-record")
+                    help="auto: with --full and N > 1 also time the other scaling mode into a labelled sub-record")
     ap.add_argument("--backend", default="hip", choices=["hip", "torch"])
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--executor", default="auto", choices=["auto", "graph", "eager"],
@@ -92,6 +103,11 @@ def parse(argv=None):
                          "are recorded as 'skipped: budget'")
     ap.add_argument("--train-size", type=int, default=54000)
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need (runs of their own): at N > 1 the "
+                         "secondary scaling sub-record and the step's all-reduce timed alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the parameters they produced (W1, b1, W2, b2) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -350,7 +366,9 @@ def _run_dp_timed(ctx, global_batch: int, mode: str, tune: dict) -> dict:
     step = tr.engine._step if a.backend == "hip" else None
     pipeline = None if step is None else {"used": bool(step.xstep_used), "why_not": step.xstep_reason or None}
     res = _dp_checks(ctx, tr)
-    ar = measure_allreduce(tr, ctx.comm, ctx.sync) if res["ok"] else {}
+    ar = (measure_allreduce(tr, ctx.comm, ctx.sync) if a.full else {"allreduce_us": None}) if res["ok"] else {}
+    if a.dump_outputs:
+        res["outputs"] = tr.engine.get_params()
     e = tr.engine
     wire = e.params.numel() * (2 if tr.xgmi is not None and tr.xgmi.wire != e.params.dtype else e.params.element_size())
     shots = 0 if tr.xgmi is None else tr.xgmi.shots
@@ -460,7 +478,7 @@ def run_tp(ctx, B: int, steps: int | None = None) -> dict:
     comm_failed = tr.comm_failed()
     ok = ok and not comm_failed
     ar = {"allreduce_us": None}
-    if R > 1 and ok:  # the step's z2 all-reduce on its own (same implementation and bytes), max over ranks
+    if R > 1 and ok and a.full:  # the step's z2 all-reduce on its own (same implementation and bytes), max over ranks
         fn = (lambda: tr._xz.allreduce_(tr.z2)) if tr._xz is not None else (lambda: comm.allreduce_(tr.z2))
         for _ in range(3):
             fn()
@@ -472,6 +490,7 @@ def run_tp(ctx, B: int, steps: int | None = None) -> dict:
         us = comm.allreduce_scalar(1e6 * (time.perf_counter() - t1) / 20, op="max")
         ar = {"allreduce_us": round(us, 2), "allreduce_bytes": int(tr.z2.numel() * 4)}
     impl = tr.allreduce_impl
+    outputs = tr.gather_params() if a.dump_outputs else None  # collective: the shards of every rank
     tr.close()
     res = {"ok": ok, "dt": dt, "images": steps * B, "global_batch": B, "per_gpu_batch": B, "parallelism": f"tp{R}",
            "checks": {"params_finite": finite, "comm_ok": not comm_failed},
@@ -480,6 +499,8 @@ def run_tp(ctx, B: int, steps: int | None = None) -> dict:
                                                                    else 0), 2) if R > 1 else None}}
     if not ok:
         res["invalid"] = "an xGMI peer wait timed out" if comm_failed else "non-finite parameters"
+    if outputs is not None:
+        res["outputs"] = outputs
     return res
 
 
@@ -546,6 +567,28 @@ def _mode_of(impl: str, ctx) -> str:
             "host-gloo": "host"}.get(impl, "rccl")
 
 
+OUTPUT_NAMES = ("W1", "b1", "W2", "b2")
+DUMP_CAP_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(directory: str, arrays, dtype: str) -> None:
+    """``directory/<name>.npy`` for the parameters the timed steps produced (float64 for f64 runs, else float32:
+    exact for fp32 parameters).  Past DUMP_CAP_BYTES in all, an array larger than its share is cut down to a fixed,
+    seeded sample of its elements (the same indices in every run, in ascending order)."""
+    import numpy as np
+
+    dt = np.float64 if dtype == "f64" else np.float32
+    arrays = [np.ascontiguousarray(x, dtype=dt) for x in arrays]
+    share = DUMP_CAP_BYTES // len(arrays) // np.dtype(dt).itemsize  # elements
+    if sum(x.nbytes for x in arrays) > DUMP_CAP_BYTES:
+        rng = np.random.default_rng(0)
+        arrays = [x if x.size <= share else x.reshape(-1)[np.sort(rng.choice(x.size, share, replace=False))]
+                  for x in arrays]
+    os.makedirs(directory, exist_ok=True)
+    for name, x in zip(OUTPUT_NAMES, arrays):
+        np.save(os.path.join(directory, name + ".npy"), x)
+
+
 def summary(ctx, res: dict) -> dict:
     a = ctx.a
     value = res["images"] / res["dt"]
@@ -592,12 +635,14 @@ def main(argv=None) -> int:
             print(f"cost model measured on this node: {cost.as_record()}", file=sys.stderr, flush=True)
     res = measure(ctx, a.scaling)
     sec = None
-    if ctx.R > 1 and a.secondary == "auto":
+    if ctx.R > 1 and a.full and a.secondary == "auto":
         other = "weak" if a.scaling == "strong" else "strong"
         # the secondary reuses the primary's choices (same bucket bytes; no second round of probes)
         sec = measure(ctx, other, parallel=res["parallel"], allreduce=res.get("allreduce_mode"))
     ok = res["ok"] and (sec is None or sec["ok"])
     if ctx.rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, res["outputs"], a.dtype)
         s = summary(ctx, res)
         rec = {
             "metric": METRIC,

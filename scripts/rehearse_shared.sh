@@ -34,7 +34,7 @@ dp1024bf_n4|--gpus 4 --hidden 1024 --dtype bf16
 dp4096_n4|--gpus 4 --hidden 4096 --allreduce xgmi2}"; do
   while IFS='|' read -r name args; do
     [ -n "$name" ] || continue
-    row "$name" $args --steps 40 --warmup 10 || rc=1
+    row "$name" $args --steps 40 --warmup 10 --full || rc=1  # (--full: the all-reduce timed alone, the secondary)
   done <<< "$spec"
 done
 python - <<'EOF'

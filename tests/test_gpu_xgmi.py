@@ -211,7 +211,7 @@ def test_bench_probes_dp_vs_tp_and_records_prediction():
 
     env = dict(os.environ, CME_SHARED_GPU="1", OMP_NUM_THREADS="2")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--hidden", "1024",
-                        "--batch", "1600", "--steps", "10", "--warmup", "2", "--tune-steps", "10"],
+                        "--batch", "1600", "--steps", "10", "--warmup", "2", "--tune-steps", "10", "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

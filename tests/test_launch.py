@@ -8,6 +8,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -15,7 +17,9 @@ def _env(**kw):
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
                         "CME_SHARED_GPU")}
-    env.update(PYTHONPATH=ROOT, OMP_NUM_THREADS="2", **kw)
+    # CPU ranks by construction: on a node that has GPUs the children must not see them (fewer GPUs than ranks is
+    # refused, and a rank that sees one binds to it)
+    env.update(PYTHONPATH=ROOT, OMP_NUM_THREADS="2", HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1", **kw)
     return env
 
 
@@ -33,7 +37,7 @@ def _records(stdout: str):
 
 def test_bench_self_launches_n_ranks(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "torch",
-                        "--steps", "3", "--warmup", "1", "--train-size", "3200"],
+                        "--steps", "3", "--warmup", "1", "--train-size", "3200", "--full"],
                        cwd=tmp_path, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     recs = _records(r.stdout)
@@ -54,12 +58,74 @@ def test_bench_self_launches_n_ranks(tmp_path):
 
 def test_bench_weak_primary_with_strong_secondary(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "torch",
-                        "--scaling", "weak", "--steps", "2", "--warmup", "1", "--train-size", "3200"],
+                        "--scaling", "weak", "--steps", "2", "--warmup", "1", "--train-size", "3200", "--full"],
                        cwd=tmp_path, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     rec = _records(r.stdout)[0]
     assert rec["scaling"] == "weak" and rec["config"]["global_batch"] == 1600
     assert rec["strong"]["global_batch"] == 800 and rec["strong"]["per_gpu_batch"] == 400
+
+
+def test_bench_plain_run_skips_what_full_adds(tmp_path):
+    """Without --full a 2-rank run times only the headline configuration: no secondary sub-record, and the
+    all-reduce is not timed on its own (allreduce_us null, no bytes or bandwidth); --dump-outputs writes the
+    parameters the timed steps produced, float32, one file per array."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "torch",
+                        "--steps", "3", "--warmup", "1", "--train-size", "3200", "--dump-outputs", str(out)],
+                       cwd=tmp_path, env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    recs = _records(r.stdout)
+    assert len(recs) == 1, r.stdout
+    rec = recs[0]
+    assert "weak" not in rec and "strong" not in rec, rec
+    assert rec["config"]["allreduce_us"] is None and "allreduce_bytes" not in rec["config"], rec["config"]
+    assert rec["steps"] == 3 and rec["value"] > 0 and rec["ms_per_step"] > 0
+    assert rec["value"] == pytest.approx(800 / (rec["ms_per_step"] * 1e-3), rel=1e-3)
+    shapes = {"W1": (100, 784), "b1": (100,), "W2": (10, 100), "b2": (10,)}
+    assert sorted(p.name for p in out.iterdir()) == sorted(n + ".npy" for n in shapes)
+    for name, shape in shapes.items():
+        x = np.load(out / f"{name}.npy")
+        assert x.dtype == np.float32 and x.shape == shape and np.isfinite(x).all(), name
+    assert np.abs(np.load(out / "b1.npy")).max() > 0  # b starts at 0: the steps moved it
+
+
+def test_bench_dump_outputs_repeatable_and_capped(tmp_path):
+    """Same arguments, same inputs: two one-rank runs dump identical arrays (the torch backend on the CPU is
+    deterministic), float64 for --dtype f64.  Past the size cap an array is cut to a fixed seeded sample."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"dump{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "torch",
+                            "--dtype", "f64", "--steps", "4", "--warmup", "1", "--train-size", "1600",
+                            "--dump-outputs", str(out)],
+                           cwd=tmp_path, env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        assert _records(r.stdout)[0]["steps"] == 4
+        dumps.append({n: np.load(out / f"{n}.npy") for n in bench.OUTPUT_NAMES})
+    for n in bench.OUTPUT_NAMES:
+        assert dumps[0][n].dtype == np.float64 and np.array_equal(dumps[0][n], dumps[1][n]), n
+
+    big = np.arange(3000, dtype=np.float64).reshape(30, 100)
+    small = np.arange(7, dtype=np.float64)
+    cap = bench.DUMP_CAP_BYTES
+    bench.DUMP_CAP_BYTES = 4 * 4 * 500  # a share of 500 float32 elements per array
+    try:
+        bench.dump_outputs(str(tmp_path / "a"), [big, small, small, small], "f32")
+        bench.dump_outputs(str(tmp_path / "b"), [big, small, small, small], "f32")
+    finally:
+        bench.DUMP_CAP_BYTES = cap
+    a, b = np.load(tmp_path / "a" / "W1.npy"), np.load(tmp_path / "b" / "W1.npy")
+    assert a.shape == (500,) and np.array_equal(a, b) and np.all(np.diff(a) > 0) and np.isin(a, big).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "b1.npy"), small.astype(np.float32))
+    assert sum(np.load(tmp_path / "a" / f"{n}.npy").nbytes for n in bench.OUTPUT_NAMES) <= 4 * 4 * 500
 
 
 def test_bench_refuses_more_gpus_than_visible(tmp_path):

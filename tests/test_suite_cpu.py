@@ -1,6 +1,8 @@
 """CPU tests of the homework suite (hw1-hw4 capabilities): native OpenMP algorithms,
 host oracles and the golden radix fixtures (hw1code/tests_q2.cpp:80-157)."""
+import gzip
 import os
+import shutil
 
 import numpy as np
 import pytest
@@ -8,7 +10,8 @@ import pytest
 from cme213_sp18_amd.suite import hw1, hw2, hw3, hw4
 from cme213_sp18_amd.utils.common import ulp_distance
 
-REF_FIXTURES = "/root/reference/hw1code/test_files"
+# the reference's text fixtures (hw1code/test_files), stored with the tests (one .gz per file)
+REF_FIXTURES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hw1_test_files")
 
 
 # ------------------------------------------------------------------ hw1
@@ -32,10 +35,12 @@ def golden():
     return hw1.make_golden_fixtures()
 
 
-def test_golden_fixtures_match_reference_files(golden):
-    ref = hw1.load_fixtures(REF_FIXTURES)
-    if ref is None:
-        pytest.skip("reference fixtures not present")
+def test_golden_fixtures_match_reference_files(golden, tmp_path):
+    for name in hw1.FIXTURE_NAMES:  # stored gzip-compressed; read back in the reference's text format
+        with gzip.open(os.path.join(REF_FIXTURES, name + ".gz"), "rb") as src, open(tmp_path / name, "wb") as dst:
+            shutil.copyfileobj(src, dst)
+    ref = hw1.load_fixtures(str(tmp_path))
+    assert ref is not None, f"fixtures missing under {REF_FIXTURES}"
     for name in hw1.FIXTURE_NAMES:
         assert np.array_equal(golden[name], ref[name]), name
 
