@@ -47,12 +47,13 @@ class TrainConfig:
     profile: bool = False       # per-phase event timing + roctx ranges (eager steps), summary at the end
     overlap_chunks: int = 0     # RCCL path: dW1 all-reduce row chunks overlapped with the backward (0 = auto)
     parallel: str = "dp"        # dp (reference scheme) | tp (hidden-dimension tensor parallel, wide layers)
+    num_classes: int = 10       # --classes: output classes (up to 64); labels must lie in [0, classes)
     gpus: int = 0               # ranks (one per GPU); 0 = WORLD_SIZE of the launcher, else 1.  N > 1 without a
                                 # launcher: the CLI starts the N ranks itself (parallel/launcher.self_launch)
 
     @property
     def H(self):
-        return [784, self.num_neuron, 10]
+        return [784, self.num_neuron, self.num_classes]
 
 
 # fpcode/main.cpp:113-152 -- "DO NOT change the following parameters"
@@ -114,6 +115,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--parallel", choices=["dp", "tp"],
                     help="dp: data parallel (default); tp: shard the hidden layer over the ranks (one z2 all-reduce "
                          "per step, every rank runs the whole global batch)")
+    ap.add_argument("--classes", dest="num_classes", type=int,
+                    help="output classes, 1..64 (default 10; e.g. 26 / 47 / 62 for the EMNIST splits): the layer sizes "
+                         "become 784-H-N, synthetic data gets N classes, and labels read with --data must lie in "
+                         "[0, N)")
     ap.add_argument("--gpus", type=int,
                     help="number of ranks, one per GPU (the reference's mpirun -np N); started here when no "
                          "launcher started this process")

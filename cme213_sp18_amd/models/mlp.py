@@ -27,8 +27,9 @@ class NeuralNetwork:
         H = [int(h) for h in H]
         if len(H) != 3:
             raise ValueError("NeuralNetwork is a 2-layer MLP: H must be [inputs, hidden, classes]")
-        if H[2] > 16:
-            raise ValueError("at most 16 output classes are supported by the fused softmax head")
+        if H[2] > 64:
+            raise ValueError("at most 64 output classes are supported (the many-class MFMA head holds 4 class tiles "
+                             "of 16)")
         self.H = H
         self.W = [np.zeros((H[1], H[0])), np.zeros((H[2], H[1]))]
         self.b = [np.zeros(H[1]), np.zeros(H[2])]

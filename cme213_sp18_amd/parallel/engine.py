@@ -89,6 +89,14 @@ class FlatLayout:
 PATHS = ("auto", "split3", "split1", "mfma")
 
 
+def fused_allreduce_eligible(backend: str, planes: int, H: int, C: int, device_type: str,
+                             bias_feature: bool) -> bool:
+    """The all-reduce fused into the weight-gradient launch (MlpEngine.fused_allreduce_slots) applies: HIP split
+    path on a GPU, H <= 128, the all-ones XT feature, and at most 16 classes -- its dW2 / db2 exchange tiles are
+    16-class, so above that DataParallelTrainer takes the separate xGMI / RCCL / host all-reduce."""
+    return bool(backend == "hip" and planes and H <= 128 and C <= 16 and device_type == "cuda" and bias_feature)
+
+
 def resolve_path(dtype: str, path: str = "auto") -> str:
     """Compute path for a dtype.
 
@@ -184,7 +192,8 @@ class MlpEngine:
             self.dZ1g = torch.zeros(H, ld, dtype=torch.bfloat16, device=dev) if self.dtype == "bf16" else self.dZ1
         # wide layers: scratch for the split-H z2 partial sums of the two-kernel head
         self.z2buf = self.dw2buf = None
-        if self.backend == "hip" and H >= 512 and self.pdt == torch.float32:
+        # (both are 16-class layouts: above 16 classes the many-class head forms z2 itself, csrc/mlp/head_mc.hip)
+        if self.backend == "hip" and H >= 512 and self.pdt == torch.float32 and C <= 16:
             self.z2buf = torch.zeros(int(hip().head_big_scratch_floats(H, ld)), dtype=torch.float32, device=dev)
             # dW2 partials the wide head leaves per 32-column tile ([tile][16][H]) for the weight-gradient launch
             self.dw2buf = torch.zeros((ld + 31) // 32 * 16 * H, dtype=torch.float32, device=dev)
@@ -446,11 +455,10 @@ class MlpEngine:
     # ------------------------------------------------ xGMI all-reduce fused into the wgrad launch
     def fused_allreduce_slots(self) -> int:
         """Flag slots (one per wgrad workgroup tile) the fused data-parallel step needs; 0 when this
-        engine cannot run it (split path, H <= 128, all-ones XT feature, no head partials)."""
+        engine cannot run it (split path, H <= 128, at most 16 classes, all-ones XT feature, no head partials)."""
         bias_feature = (self.XT.shape[0] == self.P + 1 if self.XT is not None   # loaded, or will be
                         else self.feature_major_copy)
-        if not (self.backend == "hip" and self.np and self.H <= 128 and self.device.type == "cuda"
-                and bias_feature):
+        if not fused_allreduce_eligible(self.backend, self.np, self.H, self.C, self.device.type, bias_feature):
             return 0
         return max(0, int(hip().mlp_split_fused_tiles(self.P, self.H, 1 << 30)))
 

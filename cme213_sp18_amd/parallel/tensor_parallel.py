@@ -50,6 +50,9 @@ class TensorParallelTrainer:
         self.comm = comm or NullComm()
         self.R, self.rank = self.comm.world_size, self.comm.rank
         P, H, C = nn.H
+        if C > 16:  # (the all-reduced z2 partials and the head that reads them are 16-class layouts)
+            raise ValueError(f"tensor parallelism supports at most 16 output classes (got {C}); "
+                             "use data parallelism (--parallel dp) for up to 64")
         if H % self.R:
             raise ValueError(f"hidden size {H} is not divisible by {self.R} tensor-parallel ranks")
         self.P, self.H, self.C = P, H, C

@@ -92,7 +92,7 @@ def run(cfg: TrainConfig) -> dict:
         log0(rank, f"num_neuron={cfg.num_neuron}, reg={cfg.reg}, learning_rate={cfg.learning_rate}, "
                    f"num_epochs={cfg.num_epochs}, batch_size={cfg.batch_size}, dtype={cfg.dtype}")
         t = time.perf_counter()
-        ds = load_dataset(cfg.data, cfg.data_dir, cfg.num_train, cfg.num_test, cfg.seed)
+        ds = load_dataset(cfg.data, cfg.data_dir, cfg.num_train, cfg.num_test, cfg.seed, cfg.num_classes)
         log0(rank, f"Loaded {ds.source}: train {ds.x_train.shape[0]}, dev {ds.x_dev.shape[0]}, "
                    f"test {ds.x_test.shape[0]} ({time.perf_counter() - t:.2f}s)")
         os.makedirs(cfg.outdir, exist_ok=True)
@@ -176,7 +176,10 @@ def run(cfg: TrainConfig) -> dict:
             out["par_dev_precision"] = precision(tr.predict(ds.x_dev), ds.y_dev)
             log0(rank, f"Precision on validation set for parallel training = {out['par_dev_precision']}")
             pred = tr.predict(ds.x_test)
-            save_label(os.path.join(cfg.outdir, "Pred_testset.txt"), pred)
+            if cfg.num_classes <= 10:
+                save_label(os.path.join(cfg.outdir, "Pred_testset.txt"), pred)
+            else:  # (the reference's format concatenates single digits: one label per line instead)
+                np.savetxt(os.path.join(cfg.outdir, "Pred_testset.txt"), np.asarray(pred, np.int64), fmt="%d")
             if ds.y_test is not None:
                 out["par_test_precision"] = precision(pred, ds.y_test)
             if cfg.ckpt_dir:

@@ -92,19 +92,35 @@ def load_mnist_idx(data_dir: str, max_train: int = -1, max_test: int = -1) -> Mn
     return MnistSplit(xtr, ytr, xd, yd, xt, yt, source=f"mnist:{data_dir}")
 
 
-def load_synthetic(num_train: int = NUM_TRAIN, num_test: int = NUM_TEST, seed: int = 0) -> MnistSplit:
-    x, y = synthetic_mnist(num_train + num_test, seed=seed)
+def load_synthetic(num_train: int = NUM_TRAIN, num_test: int = NUM_TEST, seed: int = 0,
+                   num_classes: int = NUM_CLASSES) -> MnistSplit:
+    x, y = synthetic_mnist(num_train + num_test, seed=seed, num_classes=num_classes)
     xtr, ytr, xd, yd = split_train_dev(x[:num_train], y[:num_train])
     return MnistSplit(xtr, ytr, xd, yd, x[num_train:], y[num_train:], source=f"synthetic(seed={seed})")
 
 
+def check_label_range(split: MnistSplit, num_classes: int) -> None:
+    """Every label of the split is a class index in [0, num_classes) -- e.g. an EMNIST label file read with
+    too small a ``--classes``, or its 1-based "letters" labels, is refused here and not inside a kernel."""
+    for name, y in (("train", split.y_train), ("dev", split.y_dev), ("test", split.y_test)):
+        if y is None or len(y) == 0:
+            continue
+        lo, hi = int(np.min(y)), int(np.max(y))
+        if lo < 0 or hi >= num_classes:
+            raise ValueError(f"{split.source}: {name} labels span [{lo}, {hi}], outside the valid range "
+                             f"[0, {num_classes}) for {num_classes} classes (--classes)")
+
+
 def load_dataset(kind: str = "synthetic", data_dir: str = "data", num_train: int = NUM_TRAIN,
-                 num_test: int = NUM_TEST, seed: int = 0) -> MnistSplit:
+                 num_test: int = NUM_TEST, seed: int = 0, num_classes: int = NUM_CLASSES) -> MnistSplit:
     if kind == "mnist":
-        return load_mnist_idx(data_dir, num_train, num_test)
-    if kind == "synthetic":
-        return load_synthetic(num_train, num_test, seed)
-    raise ValueError(f"unknown dataset kind {kind!r} (expected 'synthetic' or 'mnist')")
+        split = load_mnist_idx(data_dir, num_train, num_test)
+    elif kind == "synthetic":
+        split = load_synthetic(num_train, num_test, seed, num_classes)
+    else:
+        raise ValueError(f"unknown dataset kind {kind!r} (expected 'synthetic' or 'mnist')")
+    check_label_range(split, num_classes)
+    return split
 
 
 def label_to_y(labels: np.ndarray, num_classes: int = NUM_CLASSES) -> np.ndarray:

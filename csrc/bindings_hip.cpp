@@ -95,20 +95,21 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       "mlp_head",
       [](int dt, int mode, uintptr_t a1, int lda, uintptr_t W2, uintptr_t b2, uintptr_t labels, int H, int C,
          int n, double scale, uintptr_t Dp, int ldd, uintptr_t dZ1, int ldz, uintptr_t dZ1_bf16, uintptr_t loss,
-         uintptr_t pred, uintptr_t probs, int ldp, int shift, uintptr_t s) {
+         uintptr_t pred, uintptr_t probs, int ldp, int shift, uintptr_t s, uintptr_t dZ1_planes, int npz) {
         cme::HeadArgs h{};
         h.a1 = P<void>(a1); h.lda = lda; h.W2 = P<void>(W2); h.b2 = P<void>(b2);
         h.labels = P<int>(labels); h.H = H; h.C = C; h.n = n; h.scale = scale;
         h.D = P<void>(Dp); h.ldd = ldd; h.dZ1 = P<void>(dZ1); h.ldz = ldz; h.dZ1_bf16 = P<void>(dZ1_bf16);
         h.loss_partial = P<float>(loss); h.pred = P<int>(pred); h.probs = P<void>(probs); h.ldp = ldp;
         h.shift = shift; h.mode = mode;
+        h.dZ1_planes = P<void>(dZ1_planes); h.npz = npz;
         cme::mlp_head(to_dt(dt), h, S(s));
       },
       py::arg("dt"), py::arg("mode"), py::arg("a1"), py::arg("lda"), py::arg("W2"), py::arg("b2"),
       py::arg("labels") = 0, py::arg("H"), py::arg("C"), py::arg("n"), py::arg("scale") = 1.0,
       py::arg("D") = 0, py::arg("ldd") = 0, py::arg("dZ1") = 0, py::arg("ldz") = 0, py::arg("dZ1_bf16") = 0,
       py::arg("loss") = 0, py::arg("pred") = 0, py::arg("probs") = 0, py::arg("ldp") = 0,
-      py::arg("shift") = 1, py::arg("stream") = 0);
+      py::arg("shift") = 1, py::arg("stream") = 0, py::arg("dZ1_planes") = 0, py::arg("npz") = 0);
   m.def("mlp_head_num_blocks", &cme::mlp_head_num_blocks);
   m.def("head_big_scratch_floats", &cme::head_big_scratch_floats);
 

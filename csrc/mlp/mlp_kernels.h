@@ -63,6 +63,12 @@ int64_t head_big_scratch_floats(int H, int n);
 
 struct SplitStepArgs;
 void mlp_head(DType dt, const HeadArgs& a, hipStream_t stream);
+// the many-class output layer (head_mc.hip), 17 <= C <= 64, any H: every output mlp_head leaves in the same mode and
+// layouts, exact MFMA in the parameter dtype; dz_swz, z2_chunks and dw2part must be 0 / null.  mlp_head routes here.
+void mlp_head_mc(DType dt, const HeadArgs& a, hipStream_t stream);
+// ... and what the split path's dW2 / bias-gradient roles produce (dW2 with reg and fused SGD or into gW2, db2, and
+// db1 without the all-ones XT feature); no fused all-reduce, no dW2 partials.  mlp_split_wgrad routes here.
+void mlp_out_wgrad_mc(const SplitStepArgs& a, hipStream_t stream);
 // split path, H <= 128: forward GEMM (a1 = sigmoid(W1 X + b1), f) and the train-mode head (h, same a1) in
 // ONE launch -- the last workgroup of every 32-column tile runs the head for it.  counters: >= max_tiles
 // zero-initialised uint32 (one per 32-column tile; each launch leaves them at 0 again).

@@ -1149,7 +1149,8 @@ int64_t head_big_scratch_floats(int H, int n) { return (int64_t)cdiv(H, 64) * kC
 
 void mlp_head(DType dt, const HeadArgs& a, hipStream_t s) {
   if (a.n <= 0) return;
-  CME_REQUIRE(a.C >= 1 && a.C <= kCMax, "mlp_head: 1 <= C <= 16 required");
+  CME_REQUIRE(a.C >= 1 && a.C <= 64, "mlp_head: 1 <= C <= 64 required");
+  if (a.C > kCMax) return mlp_head_mc(dt, a, s);  // the many-class head (head_mc.hip)
   if (a.z2part && a.z2_chunks > 0 && dt != DType::F64 && a.mode == HEAD_TRAIN && a.C <= 16) {
     // partials left by the forward GEMM
     CME_REQUIRE((int64_t)a.z2_chunks * 16 * a.lda < (int64_t)kOOB / 4 && (int64_t)a.H * a.lda < (int64_t)kOOB / 4,

@@ -1669,6 +1669,17 @@ void mlp_split_wgrad(const SplitStepArgs& a, hipStream_t s) {
   CME_REQUIRE((int64_t)a.H * a.ld * 2 * a.npz < (int64_t)kOOB && (int64_t)a.P * a.ldxt < (int64_t)kOOB,
               "split path: operand too large for 32-bit buffer offsets");
   CME_REQUIRE(a.w1_row0 >= 0 && (a.w1_rows < 0 || a.w1_row0 + a.w1_rows <= a.H), "wgrad: bad dW1 row range");
+  if (a.C > 16 && (a.wg_parts & 2)) {  // many classes: the dW2 / bias roles are 16-class; this launch without them
+    // (the small launch's t2 / tb, the wide engines' t2f / tbf), then the output layer's own launch (head_mc.hip)
+    CME_REQUIRE(a.xf_world == 0, "wgrad: the all-reduce fused into the weight-gradient launch needs C <= 16 "
+                                 "(more classes: the separate all-reduce)");
+    CME_REQUIRE(!a.dw2part, "wgrad: dW2 partials from the head need C <= 16");
+    SplitStepArgs b = a;
+    b.wg_parts &= ~2;
+    mlp_split_wgrad(b, s);
+    mlp_out_wgrad_mc(a, s);
+    return;
+  }
   const bool fused = a.xf_world > 0;
   const bool big = big_wgrad_ok(a) && !fused;
   const bool do_w1 = (a.wg_parts & 1) && a.w1_rows != 0, do_roles = (a.wg_parts & 2) != 0;

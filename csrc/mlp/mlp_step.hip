@@ -199,7 +199,8 @@ StepForm MlpStep::plan(int64_t off, int n, double scale, double reg, double lr, 
       // wide layers: the forward GEMM also leaves the head's z2 partials (unless only the head runs)
       SplitStepArgs& f = p.f;
       f = a;
-      f.z2part = (z2p && !(parts & 8)) ? P_<float>(z2p) : nullptr;
+      // (the partials are 16-class: with more classes the forward leaves none and the many-class head forms z2)
+      f.z2part = (z2p && !(parts & 8) && C <= 16) ? P_<float>(z2p) : nullptr;
       h.z2_chunks = f.z2part ? mlp_split_fwd1_z2_chunks(f) : 0;
       // with the all-ones XT feature nothing reads dZ1 in fp32 on the wide path (db1 comes out of
       // the dW1 GEMM over the planes): skip those 4 B/element of HBM writes
