@@ -7,7 +7,11 @@ launch; its XCD-local barrier's form from --bar), ``--rounds`` times alternated;
 of --reps steps.  With --stamps K, the pipeline also records per-workgroup phase stamps of its first K steps
 (s_memrealtime): forward + head, first barrier, dW1 / role, second barrier -- medians per XCD.
 
-    python bench/xstep_ab.py [--cols 800] [--reps 200] [--rounds 2] [--bar 0 1] [--stamps 40] [--fha-stamps 30]
+--pix adds a form per value of the dW1 tiles' pixel operand (``MlpStep.xstep_pix``: 0 the feature-major copy, 1 the
+forward's fragment-ordered copy through LDS); --w1-stamps K records the dW1 tiles' per-wave stamps for each of them.
+
+    python bench/xstep_ab.py [--cols 800] [--reps 200] [--rounds 2] [--bar 0 1] [--pix 0 1] [--stamps 40]
+                             [--w1-stamps 40] [--fha-stamps 30]
 """
 from __future__ import annotations
 
@@ -28,9 +32,13 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--bar", type=int, nargs="*", default=[3], help="MlpStep.xstep_bar values (XStepPlan::bar)")
     ap.add_argument("--pf", type=int, nargs="*", default=[0], help="MlpStep.xstep_pf values (XStepPlan::npf)")
+    ap.add_argument("--pix", type=int, nargs="*", default=[0],
+                    help="MlpStep.xstep_pix values (XStepPlan::pix: the dW1 tiles' pixel operand), barrier form 3 only")
     ap.add_argument("--rm", action="store_true",
                     help="also the pipeline's row-major form on plans the fragment-ordered form takes (MlpStep.dz_swz = 0)")
     ap.add_argument("--stamps", type=int, default=0)
+    ap.add_argument("--w1-stamps", type=int, default=0,
+                    help="per-wave stamps of the dW1 tiles in the last of K steps, for each --pix form")
     ap.add_argument("--fha-stamps", type=int, default=0, help="forward + head body stamps of the last of K steps")
     ap.add_argument("--gemm-stamps", action="store_true",
                     help="with --fha-stamps: also the forward K loop's per-wave stamps (stored mid-body: they perturb)")
@@ -65,14 +73,15 @@ def main(argv=None):
         def walk(count, g0=0):
             st.run_steps(g0, count, n, 0, n, N, 1.0 / n, 1e-4, 1e-3, 1, stream)
 
-        forms = [("two_launch", 0, 1, 0)] + [(f"xstep_bar{b}_pf{q}", -1, b, q) for b in a.bar for q in a.pf
-                                             if b == 1 or q == 0]
+        forms = [("two_launch", 0, 1, 0, 0)] + [
+            (f"xstep_bar{b}_pf{q}" + (f"_pix{px}" if px else ""), -1, b, q, px)
+            for b in a.bar for q in a.pf for px in a.pix if (b == 1 or q == 0) and (b == 3 or px == 0)]
         if a.rm:
-            forms.append(("xstep_rm", -1, 3, 0))
+            forms.append(("xstep_rm", -1, 3, 0, 0))
         dz0 = st.dz_swz
         for rnd in range(a.rounds):
-            for name, xs, b, q in forms:
-                st.xstep, st.xstep_bar, st.xstep_pf = xs, b, q
+            for name, xs, b, q, px in forms:
+                st.xstep, st.xstep_bar, st.xstep_pf, st.xstep_pix = xs, b, q, px
                 st.dz_swz = 0 if name == "xstep_rm" else dz0
                 walk(20)
                 torch.cuda.synchronize()
@@ -112,6 +121,31 @@ def main(argv=None):
             per = np.diff(g0[:, 0]) / 100
             emit({"n": n, "H": a.hidden, "bar": a.bar[-1], "stamps_steps": k, "step_period_median_us": round(float(np.median(per)), 3),
                   "per_xcd_median_us_from_step_start": rows})
+        if a.w1_stamps:
+            # the dW1 tiles' per-wave stamps of the LAST step of a K-step plan (the diagnostics build; XStepPlan::
+            # w1stamps), per pixel form: medians over the waves that have a K range, relative to the wave's entry into
+            # the tile -- gate passed, first burst's operands back (that stamp waits for them), K loop done, reduced,
+            # epilogue done
+            k = a.w1_stamps
+            for px in a.pix:
+                buf = torch.zeros(256 * 8 * 6, dtype=torch.int64, device="cuda")
+                st.xstep, st.xstep_bar, st.xstep_pf, st.xstep_pix = -1, 3, 0, px
+                st.xs_w1stamps = buf.data_ptr()
+                walk(k)
+                torch.cuda.synchronize()
+                st.xs_w1stamps = 0
+                b = buf.cpu().numpy().astype(np.int64)
+                w4, g2 = b[: 256 * 8 * 4].reshape(256, 8, 4), b[256 * 8 * 4:].reshape(256, 8, 2)
+                m = (w4[:, :, 0] > 0) & (g2[:, :, 1] > 0)  # (waves of dW1 tiles that ran a K loop)
+                ent = w4[:, :, 0]
+                cols = {"gate_passed": g2[:, :, 0], "first_operands_back": g2[:, :, 1], "kloop_done": w4[:, :, 1],
+                        "reduced": w4[:, :, 2], "epilogue_done": w4[:, :, 3]}
+                emit({"n": n, "H": a.hidden, "pix": px, "w1_stamps_last_of": k, "waves": int(m.sum()),
+                      "kernel_error": bool(e.kernel_error()),
+                      "median_us_from_tile_entry": {kk: round(float(np.median((v - ent)[m])) / 100, 3)
+                                                    for kk, v in cols.items()},
+                      "p90_us_from_tile_entry": {kk: round(float(np.percentile((v - ent)[m], 90)) / 100, 3)
+                                                 for kk, v in cols.items()}})
         if a.fha_stamps:
             # the forward + head body's own stamps (fha_body: entry, z2 partial published, all partials gathered,
             # end) and the K loop's per-wave stamps (wsk_tile) for the LAST step of a K-step plan, relative to the

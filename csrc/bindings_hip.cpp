@@ -193,10 +193,12 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       .def_readwrite("xstep", &MlpStep::xstep)
       .def_readwrite("xstep_bar", &MlpStep::xstep_bar)
       .def_readwrite("xstep_pf", &MlpStep::xstep_pf)
+      .def_readwrite("xstep_pix", &MlpStep::xstep_pix)
       .def_readonly("xstep_used", &MlpStep::xstep_used)
       .def_readonly("xstep_reason", &MlpStep::xstep_reason)
       .def_readwrite("xs_stamps", &MlpStep::xs_stamps)
       .def_readwrite("xs_stamp_steps", &MlpStep::xs_stamp_steps)
+      .def_readwrite("xs_w1stamps", &MlpStep::xs_w1stamps)
       .def_readwrite("lazy_planes", &MlpStep::lazy_planes)
       .def_readwrite("planes_stale", &MlpStep::planes_stale)
       .def_readwrite("dw2p", &MlpStep::dw2p)

@@ -259,9 +259,16 @@ struct XStepPlan {
                            // column tiles' dZ1: EpiW1Gate), 3 both fine-grained (the next step's forward waves wait
                            // for their own dW1 tiles, wave 7 for all of them and the role: fha_body PsGate)
                            // -- n = 800 walking step: 0 ~14, 1 11.0, 2 10.8, 3 9.85 us (profiles/r6/xstep_ab_r6i.jsonl)
+  int pix = 1;             // the dW1 tiles' pixel operand (fragment-ordered form, bar 3): 0 the feature-major copy XT0,
+                           // 1 the forward's copy Xs0 out of the XCD's L2, transposed through LDS (xstep.hip PIX)
   unsigned long long* stamps = nullptr;  // diagnostics: [stamp_steps][8][32][4] s_memrealtime per workgroup
   int stamp_steps = 0;
+  // diagnostics (barrier form 3): the dW1 tiles' per-wave stamps of the plan's LAST step, by launch workgroup --
+  // [256][8 waves][4]: tile entered, K loop done, reduced, epilogue done; then [256][8][2]: gate passed, the first
+  // burst's operands back
+  unsigned long long* w1stamps = nullptr;
 };
+constexpr int64_t kXstepW1Stamps = 256 * 8 * 6;
 bool mlp_xstep_ok(const SplitStepArgs& a, const HeadArgs& h);
 int mlp_xstep_rm(const SplitStepArgs& a);  // the row-major form's dW1 vector form (0: the form does not apply)
 int mlp_xstep_workers(const SplitStepArgs& a);

@@ -152,6 +152,7 @@ struct MlpStep {
   // partials, fused SGD, one process, steps on the 16-sample grid); -1 auto (on), 0 off, 1 required (an error if
   // the plan does not qualify).  xstep_bar: XStepPlan::bar (the XCD-local barrier's form).
   int xstep = -1, xstep_bar = 3, xstep_pf = 0;  // xstep_pf: XStepPlan::npf
+  int xstep_pix = 1;      // XStepPlan::pix: the dW1 tiles' pixel operand (0 XT, 1 the forward's copy through LDS)
   int xstep_used = 0;     // the last run_steps ran as one xstep launch (tests, bench records)
   std::string xstep_reason = "";  // why the last run_steps did not take the pipeline ("" when it did)
   unsigned xs_ep = 1, xs_launch = 0;  // the next step's granule tag; launches so far (control bank)
@@ -159,6 +160,7 @@ struct MlpStep {
   float *xs_dx = nullptr, *xs_b2x = nullptr;
   uintptr_t xs_stamps = 0;  // diagnostics: [xs_stamp_steps][8][32][4] uint64 (bench/stamps_xstep.py)
   int xs_stamp_steps = 0;
+  uintptr_t xs_w1stamps = 0;  // diagnostics: XStepPlan::w1stamps, kXstepW1Stamps uint64 (bench/xstep_ab.py --w1-stamps)
   float xscale = 1.f;    // split path: inputs are uint8 * xscale
   uintptr_t W1p = 0, dZ1p = 0;
   // wide split3 layers: the in-place dW1 update skips the W1-plane refresh (SplitStepArgs::w1_planes_lazy) and

@@ -299,6 +299,13 @@ template <class E, class = void>
 struct HasBeforeKloop : std::false_type {};
 template <class E>
 struct HasBeforeKloop<E, std::void_t<decltype(std::declval<E&>().before_kloop(0, 0))>> : std::true_type {};
+// ... and a diagnostics epilogue may ask to be told when the first burst's operands are all back:
+// epi.first_operands_back() is called by every wave with a K range after its first burst's loads, before their first
+// use (the hook itself waits for them and stamps; xstep.hip's diagnostics build).  Epilogues without it: nothing.
+template <class E, class = void>
+struct HasFirstOperandsBack : std::false_type {};
+template <class E>
+struct HasFirstOperandsBack<E, std::void_t<decltype(std::declval<E&>().first_operands_back())>> : std::true_type {};
 
 // One workgroup = KS waves computing the (16*MB) x (16*NB) tile at (m0, n0)
 // of C = A * B with K split across the waves.  On return, `epi(row, col, v)`
@@ -340,12 +347,33 @@ __host__ __device__ __forceinline__ int64_t xs_off(int64_t s, int k, int npair) 
 // CPA (fp32 A only): the A loads' cache policy -- kSc1 for an operand another workgroup of the same launch rewrote
 // since this CU last read it (the XCD-local step pipeline, xstep.hip: W1s and dZ1 -- fragment-ordered or row-major --
 // are read with L1-bypassing, L2-served loads; a plain load could return this CU's stale L1 line)
+//
+// BLDS (u8 B, VEC == 3, NB == 2, K = samples: the XCD-local step pipeline's dW1 tile): B is not the feature-major
+// pixels but the FORWARD's fragment-ordered copy (xs_off; ldb = its number of 64-feature pairs, B = the step's first
+// sample tile), which the XCD's L2 already holds from the forward.  There a 16-sample tile keeps the tile's 32
+// features g.n0 .. g.n0 + 31 as two adjacent 256-byte blocks of 16 rows (samples) x 16 bytes (features), and lane
+// (c, grp) needs one COLUMN of such a block per chunk pair -- the 16 bytes its feature-major load returns.  So each
+// wave pulls the 2 U sample tiles of a burst with U 16-byte loads per lane (512-byte contiguous runs), writes them to
+// its own U KB of `btr` (LDS, KS * U KB in all, 16-byte aligned; wave-private, so no barrier) and reads the columns
+// back with ds_read_b64_tr_b8.  That instruction's lane mapping, established with a one-wave probe on gfx950 (a
+// known byte pattern, each lane reading 8 bytes at its own address): within each block of 16 lanes, lane i's result
+// byte j is byte i % 8 of the 8 bytes that lane 2 j + i / 8 of the block addressed.  With lane i addressing bytes
+// 8 (i & 1) .. + 7 of row (i >> 1) + 8 h, lane c therefore receives byte c of rows 8 h .. 8 h + 7: h = 0 is chunk
+// u's operand, h = 1 chunk u + 1's -- the same bytes in the same registers as the feature-major load.  (Needs EXEC
+// all ones and 8-byte aligned addresses: every wave of the workgroup runs this with all lanes.)  Sample tiles past
+// this wave's kend read zero (A is zero there); column `ones_col` (the bias column, which the fragment-ordered copy
+// does not have) is byte 1 for every sample, synthesized in registers; pairs past ldb read zero.
+// The pixel loads go first in each burst, so their LDS round trip waits for them alone.  (Running the first burst's
+// pixel path BEFORE epi.before_kloop -- the pixels do not depend on what the gate waits for -- measured slower, the
+// walking step 9.30-9.34 -> 9.49-9.52 us at n = 800: the wave's poll and its dZ1 loads then start ~0.7 us later,
+// profiles/r7/README.md.)
 template <typename T, int MB, int NB, int KS, bool AK, bool BK, int VEC, int U, int NPA = 1, typename TB = T,
-          typename TA = T, bool ASWZ = false, bool BSWZ = false, int CPA = 0, class Epi>
+          typename TA = T, bool ASWZ = false, bool BSWZ = false, int CPA = 0, bool BLDS = false, class Epi>
 __device__ __forceinline__ void wsk_tile(const TA* __restrict__ A, int lda, const TB* __restrict__ B, int ldb,
                                          TileGeom g, Epi& epi,
                                          typename MmaTraits<T>::acc_t* __restrict__ red, int plane_bytes = 0,
-                                         unsigned long long* stamps = nullptr) {
+                                         unsigned long long* stamps = nullptr, unsigned char* btr = nullptr,
+                                         int ones_col = -1) {
   using Tr = MmaTraits<T>;
   using accv_t = typename Tr::accv_t;
   using acc_t = typename Tr::acc_t;
@@ -405,6 +433,47 @@ __device__ __forceinline__ void wsk_tile(const TA* __restrict__ A, int lda, cons
   const int kbeg = wave * cpw * KC;
   const int kend = min(g.K, (wave + 1) * cpw * KC);
 
+  // BLDS: a burst's pixels from the fragment-ordered copy -- xs_issue: the 2 U sample tiles from kc on, U loads per
+  // lane (load i: lanes 0-31 sample tile 2 i, lanes 32-63 tile 2 i + 1, 16 bytes each of the tile's 512);
+  // xs_finish: through this wave's LDS region into the operand registers
+  static_assert(!BLDS || (std::is_same_v<TB, uint8_t> && VEC == 3 && NB == 2 && !BSWZ && V == 8),
+                "pixels through LDS: the u8 B operand in chunk pairs, a 32-feature tile");
+  using xsw_t = decltype(__builtin_amdgcn_raw_buffer_load_b128(rsB, 0, 0, 0));
+  typedef int tr8_t __attribute__((ext_vector_type(2)));
+  [[maybe_unused]] auto xs_issue = [&](int kc, xsw_t (&w)[U]) {
+    if constexpr (BLDS) {
+      const int p = g.n0 >> 6;
+      const int fb = p * 1024 + ((g.n0 >> 5) & 1) * 512 + (lane & 31) * 16;
+#pragma unroll
+      for (int i = 0; i < U; ++i) {
+        const int ks = kc + 32 * i + 16 * (lane >> 5);  // the tile's first sample
+        const bool ok = ks + 16 <= kend && p < ldb;
+        w[i] = __builtin_amdgcn_raw_buffer_load_b128(rsB, ok ? (ks >> 4) * ldb * 1024 + fb : kOOB, 0, 0);
+      }
+    }
+  };
+  [[maybe_unused]] auto xs_finish = [&](const xsw_t (&w)[U], T (&bo)[BLDS ? U : 1][NB][V]) {
+    if constexpr (BLDS) {
+      unsigned char* my = btr + wave * (U * 1024);
+#pragma unroll
+      for (int i = 0; i < U; ++i)
+        *(__attribute__((address_space(3))) xsw_t*)(my + i * 1024 + lane * 16) = w[i];
+#pragma unroll
+      for (int pp = 0; pp < U / 2; ++pp)
+#pragma unroll
+        for (int j = 0; j < NB; ++j)
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            tr8_t v = __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) tr8_t*)(
+                my + (pp * 4 + grp) * 512 + j * 256 + ((c >> 1) + 8 * h) * 16 + 8 * (c & 1)));
+            const bool one = g.n0 + 16 * j + c == ones_col;
+            U8Raw<1> r;
+            r.w[0] = one ? 0x01010101u : (unsigned)v[0];
+            r.w[1] = one ? 0x01010101u : (unsigned)v[1];
+            widen_u8<1>(r, bo[2 * pp + h][j]);
+          }
+    }
+  };
   if constexpr (HasBeforeKloop<Epi>::value) epi.before_kloop(kbeg, kend);
   constexpr bool AF32 = std::is_same_v<TA, float> && !std::is_same_v<T, float>;
   static_assert(!AF32 || (std::is_same_v<T, __hip_bfloat16> && NPA == 3 && AK), "fp32 A: split3 bf16, K-contiguous");
@@ -426,6 +495,9 @@ __device__ __forceinline__ void wsk_tile(const TA* __restrict__ A, int lda, cons
     float ar[AF32 ? U : 1][MB][V];
     T bf[U][NB][V];
     U8Raw<VEC == 3 ? 1 : VEC> braw[BU8 ? U : 1][NB];
+    [[maybe_unused]] T bfx[BLDS ? U : 1][NB][V];  // BLDS: the burst's B operand
+    [[maybe_unused]] xsw_t xw[U];
+    if constexpr (BLDS) xs_issue(kc, xw);  // (first: their LDS round trip then waits for them alone)
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int k = VEC == 3 ? kc + (u & ~1) * KC + 2 * V * grp + (u & 1) * V : kc + u * KC + V * grp;
@@ -451,7 +523,8 @@ __device__ __forceinline__ void wsk_tile(const TA* __restrict__ A, int lda, cons
       }
 #pragma unroll
       for (int j = 0; j < NB; ++j) {
-        if constexpr (BU8) {
+        if constexpr (BLDS) {
+        } else if constexpr (BU8) {
           static_assert(std::is_same_v<T, __hip_bfloat16> && BK, "u8 B operand: bf16 MFMA, K-contiguous");
           if constexpr (VEC == 3) {
             if ((u & 1) == 0) {  // the pair's 16 bytes: words 0-1 -> chunk u, words 2-3 -> chunk u + 1
@@ -477,9 +550,17 @@ __device__ __forceinline__ void wsk_tile(const TA* __restrict__ A, int lda, cons
     // turns the burst into U dependent memory round trips (measured: 25
     // vmcnt(0) waits per wave in fwd1).  With it: one wait ladder per burst.
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (HasFirstOperandsBack<Epi>::value) {
+      if (kc == kbeg) epi.first_operands_back();
+    }
+    if constexpr (BLDS) xs_finish(xw, bfx);
+    auto& bop = [&]() -> auto& {
+      if constexpr (BLDS) return bfx;
+      else return bf;
+    }();
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      if constexpr (BU8) {
+      if constexpr (BU8 && !BLDS) {
 #pragma unroll
         for (int j = 0; j < NB; ++j) widen_u8<VEC == 3 ? 1 : VEC>(braw[u][j], bf[u][j]);
       }
@@ -499,7 +580,7 @@ __device__ __forceinline__ void wsk_tile(const TA* __restrict__ A, int lda, cons
 #pragma unroll
         for (int i = 0; i < MB; ++i)
 #pragma unroll
-          for (int j = 0; j < NB; ++j) Tr::mma(af[u][p][i], bf[u][j], acc[i][j]);
+          for (int j = 0; j < NB; ++j) Tr::mma(af[u][p][i], bop[u][j], acc[i][j]);
     }
   }
 

@@ -16,7 +16,8 @@
 //     own body, in its PS form: z2 partials out as data-tagged granules (tag = the plan's step number, slab by step
 //     parity), the all-gather, softmax, D, the dW2 partials and dZ1 -- then, after the XCD's first barrier, the dW1
 //     tile (rt, feature tile j) over the whole batch with the fused reg + SGD update of W1 / W1s / b1 (EpiW1, the
-//     two-launch epilogue);
+//     two-launch epilogue) -- its pixel operand out of the forward's fragment-ordered copy, which this XCD's L2 holds,
+//     not the feature-major copy (PIX below);
 //   * slot nw is the XCD's role workgroup: after the first barrier it sums the dW2 partials of W2[:, rt rows] (EpiW2)
 //     and reduces D into db2 -- redundantly on every XCD, in the same order, into that XCD's own copy of b2 (XCD 0
 //     also writes the master b2 at the plan's last step);
@@ -198,6 +199,27 @@ struct EpiW1Gate : EpiW1 {
   }
 };
 
+// The diagnostics build's gated epilogue: per-wave stamps (s_memrealtime, lane 0) when the wave's gate has passed and
+// when its first burst's operands are all back (it waits for them: the stamp perturbs what it measures); wsk_tile's
+// own stamps give the tile's entry, K loop done, reduced and epilogue done (XStepPlan::w1stamps).
+struct EpiW1GateDiag : EpiW1Gate {
+  unsigned long long* ws;  // this wave's two stamps (nullptr: none)
+  __device__ void put(int i) {
+    const unsigned long long tt = __builtin_amdgcn_s_memrealtime();
+    if ((threadIdx.x & 63) == 0) ws[i] = tt;
+  }
+  __device__ void before_kloop(int kbeg, int kend) {
+    EpiW1Gate::before_kloop(kbeg, kend);
+    if (ws) put(0);
+  }
+  __device__ void first_operands_back() {
+    if (ws) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      put(1);
+    }
+  }
+};
+
 // The samples of a run_steps plan's steps: consecutive global batches of B from gstart0, wrapping to 0 when one
 // would pass N_end (MlpStep::run_steps), this rank's shard at +shard_off.  off() is the current step's first sample,
 // next() the following step's; advance() moves on by one step.
@@ -223,13 +245,22 @@ struct XsWalk {
 // a step (mlp_split_wgrad vec 1 / 3) -- or, n % 4 == 0, 2 x 16-byte vectors with the tail past n zeroed in registers
 // (RM 4: the same MFMA operands as the two-launch step's element loads, vec 2; n = 100 walking step 9.25 -> 8.90 us,
 // profiles/r6/rm_form/), so the bits are its bits.
-template <int BAR, int FG, bool DIAG = false, int HK = 0, int RM = 0>
+// PIX (RM 0, barrier form 3): where the dW1 tile's pixel operand comes from (XStepPlan::pix).  0: the feature-major
+// copy XT, as the two-launch step reads it -- the same pixels the forward just pulled, at other addresses, so every
+// XCD fetches the batch a second time through the fabric.  1: the forward's fragment-ordered copy, which this XCD's
+// L2 holds, transposed through a wave-private LDS region (wsk_tile BLDS; the MFMA operands are the same registers,
+// so the bits are the same) -- the default: fabric read requests per step 97.5k -> 60.1k, L2 hit rate 76.6 -> 86.9 %,
+// the wave's first operands back 0.64 us sooner, walking step at n = 800 9.42-9.45 -> 9.30-9.34 us
+// (profiles/r7/README.md).
+template <int BAR, int FG, bool DIAG = false, int HK = 0, int RM = 0, int PIX = 0>
 __global__ __launch_bounds__(512) void xstep_kernel(SplitStepArgs a, HeadArgs h, XStepPlan p, int tm, int tn,
                                                     int t1n) {
   static_assert(FG == 0 || BAR == 1, "the fine-grained barriers need the flag line");
   static_assert(RM == 0 || (BAR == 1 && FG == 2), "the row-major form: barrier form 3");
+  static_assert(PIX == 0 || (RM == 0 && FG == 2), "the pixels through LDS: the fragment-ordered form, barrier form 3");
   constexpr int kSwz = RM == 0 ? 7 : 1;  // fha_body: fragment-ordered W1 (+ pixels and dZ1 in form 0)
   __shared__ __attribute__((aligned(16))) float red[8 * 1 * 2 * 4 * 64];  // both GEMM tiles' K reductions
+  __shared__ __attribute__((aligned(16))) unsigned char pixl[PIX ? 8 * 4 * 1024 : 16];  // PIX: 4 KB per dW1 wave
   __shared__ int s_slot, s_stop;
   __shared__ unsigned s_x;
   const int t = threadIdx.x;
@@ -345,14 +376,27 @@ __global__ __launch_bounds__(512) void xstep_kernel(SplitStepArgs a, HeadArgs h,
         const EpiW1 e1{a.W1, a.gW1, static_cast<bf16*>(a.W1p), (size_t)a.H * a.P, a.P, 1, 0, reg, lr, a.xscale, {},
                        a.b1, a.gb1, 0, nullptr};
         if constexpr (FG > 0) {
-          EpiW1Gate epi{e1, &bar, 2 * s, tn, &s_stop};
-          epi.W1s = a.W1s;
-          if constexpr (RM == 0)
-            wsk_tile<bf16, 1, 2, 8, true, true, 3, 4, 3, uint8_t, float, true, false, kSc1>(
-                a.dZ1, (ld + 63) / 64, static_cast<const uint8_t*>(p.XT0) + off, a.ldxt, g, epi, red, 0, nullptr);
-          else
-            wsk_tile<bf16, 1, 2, 8, true, true, RM, 4, 3, uint8_t, float, false, false, kSc1>(
-                a.dZ1, ld, static_cast<const uint8_t*>(p.XT0) + off, a.ldxt, g, epi, red, 0, nullptr);
+          auto dw1 = [&](auto& epi, unsigned long long* wst) {
+            epi.W1s = a.W1s;
+            if constexpr (RM == 0 && PIX != 0)
+              wsk_tile<bf16, 1, 2, 8, true, true, 3, 4, 3, uint8_t, float, true, false, kSc1, true>(
+                  a.dZ1, (ld + 63) / 64, p.Xs0 + off / 16 * p.xs_tile, (int)(p.xs_tile / 1024), g, epi, red, 0, wst,
+                  pixl, a.P);
+            else if constexpr (RM == 0)
+              wsk_tile<bf16, 1, 2, 8, true, true, 3, 4, 3, uint8_t, float, true, false, kSc1>(
+                  a.dZ1, (ld + 63) / 64, static_cast<const uint8_t*>(p.XT0) + off, a.ldxt, g, epi, red, 0, wst);
+            else
+              wsk_tile<bf16, 1, 2, 8, true, true, RM, 4, 3, uint8_t, float, false, false, kSc1>(
+                  a.dZ1, ld, static_cast<const uint8_t*>(p.XT0) + off, a.ldxt, g, epi, red, 0, wst);
+          };
+          if constexpr (DIAG) {  // (the last step's stamps stay: [256 workgroups][8 waves][4], then [256][8][2])
+            EpiW1GateDiag epi{{e1, &bar, 2 * s, tn, &s_stop},
+                              p.w1stamps ? p.w1stamps + 256 * 8 * 4 + ((size_t)blockIdx.x * 8 + (t >> 6)) * 2 : nullptr};
+            dw1(epi, p.w1stamps);
+          } else {
+            EpiW1Gate epi{e1, &bar, 2 * s, tn, &s_stop};
+            dw1(epi, nullptr);
+          }
         } else {
           EpiW1 epi = e1;
           epi.W1s = a.W1s;
@@ -490,18 +534,25 @@ void mlp_xstep(const SplitStepArgs& a, const HeadArgs& h, const XStepPlan& p, hi
               "xstep: every step must start a 16-sample tile of the fragment-ordered pixels (row-major form: 4-byte "
               "aligned pixel columns)");
   CME_REQUIRE(a.ld >= a.n && a.ld % 16 == 0, "xstep: activation pitch");
-  const bool diag = p.stamps || a.stamps || h.stamps || a.ag_test_skip >= 0;
+  const bool diag = p.stamps || p.w1stamps || a.stamps || h.stamps || a.ag_test_skip >= 0;
   CME_REQUIRE(!diag || p.bar == 3 || p.bar == 1,
               "xstep: the stamps and the hand-off test hook exist in the diagnostics builds of barrier forms 1 and 3");
   CME_REQUIRE(!rm || (p.bar == 3 && p.npf == 0 && !diag), "xstep: the row-major form exists in barrier form 3 only");
+  // (pix is honoured by the fragment-ordered form of barrier form 3 and its diagnostics build; every other form reads
+  // XT)
+  CME_REQUIRE(p.pix == 0 || p.pix == 1, "xstep: the dW1 pixel operand's form is 0 (XT) or 1 (the forward's copy)");
   if (rm == 1) xstep_kernel<1, 2, false, 7, 1><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
   else if (rm == 4) xstep_kernel<1, 2, false, 7, 4><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
   else if (rm == 3) xstep_kernel<1, 2, false, 7, 3><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
+  else if (diag && p.bar == 3 && p.pix == 1)
+    xstep_kernel<1, 2, true, 0, 0, 1><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
   else if (diag && p.bar == 3) xstep_kernel<1, 2, true><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
   else if (diag) xstep_kernel<1, 0, true><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
   // (the production form keeps fha_body's three no-op runtime tests, HK = 7: measured 9.55-9.61 us against 9.81-9.86
   // without them and 9.62-9.94 with any one or two -- the compiler schedules the body differently; alternated four
   // and three times on two boxes, profiles/r6/hk/)
+  else if (p.bar == 3 && p.pix == 1)
+    xstep_kernel<1, 2, false, 7, 0, 1><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
   else if (p.bar == 3) xstep_kernel<1, 2, false, 7><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
   else if (p.bar == 2) xstep_kernel<1, 1><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
   else if (p.bar == 1) xstep_kernel<1, 0><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
