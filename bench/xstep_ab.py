@@ -3,15 +3,19 @@
 
 For each batch size: the walking native loop (``MlpStep.run_steps`` over consecutive batches, as bench.py's timed
 region runs it) with ``xstep = 0`` (two launches per step) and ``xstep = -1`` (the whole plan in one persistent
-launch; its XCD-local barrier's form from --bar), ``--rounds`` times alternated; us/step = best of 5 event-timed plans
-of --reps steps.  With --stamps K, the pipeline also records per-workgroup phase stamps of its first K steps
-(s_memrealtime): forward + head, first barrier, dW1 / role, second barrier -- medians per XCD.
+launch), ``--rounds`` times alternated; us/step = best of 5 event-timed plans of --reps steps.  With --stamps K, the
+pipeline also records per-workgroup phase stamps of its first K steps (s_memrealtime): forward + head, first arrival,
+dW1 / role, second arrival -- medians per XCD.
 
 --pix adds a form per value of the dW1 tiles' pixel operand (``MlpStep.xstep_pix``: 0 the feature-major copy, 1 the
 forward's fragment-ordered copy through LDS); --w1-stamps K records the dW1 tiles' per-wave stamps for each of them.
 
-    python bench/xstep_ab.py [--cols 800] [--reps 200] [--rounds 2] [--bar 0 1] [--pix 0 1] [--stamps 40]
-                             [--w1-stamps 40] [--fha-stamps 30]
+Form names: ``xstep`` (pix 0) and ``xstep_pix1`` are the rows that profiles/r6 and profiles/r7 call
+``xstep_bar3_pf0`` and ``xstep_bar3_pf0_pix1`` -- the pipeline had other barrier forms (bar 0-2) and prefetch
+workgroups (pf > 0) then; their rows there have no counterpart now.
+
+    python bench/xstep_ab.py [--cols 800] [--reps 200] [--rounds 2] [--pix 0 1] [--stamps 40] [--w1-stamps 40]
+                             [--fha-stamps 30]
 """
 from __future__ import annotations
 
@@ -30,10 +34,8 @@ def main(argv=None):
     ap.add_argument("--cols", type=int, nargs="*", default=[800])
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=2)
-    ap.add_argument("--bar", type=int, nargs="*", default=[3], help="MlpStep.xstep_bar values (XStepPlan::bar)")
-    ap.add_argument("--pf", type=int, nargs="*", default=[0], help="MlpStep.xstep_pf values (XStepPlan::npf)")
     ap.add_argument("--pix", type=int, nargs="*", default=[0],
-                    help="MlpStep.xstep_pix values (XStepPlan::pix: the dW1 tiles' pixel operand), barrier form 3 only")
+                    help="MlpStep.xstep_pix values (XStepPlan::pix: the dW1 tiles' pixel operand)")
     ap.add_argument("--rm", action="store_true",
                     help="also the pipeline's row-major form on plans the fragment-ordered form takes (MlpStep.dz_swz = 0)")
     ap.add_argument("--stamps", type=int, default=0)
@@ -73,15 +75,13 @@ def main(argv=None):
         def walk(count, g0=0):
             st.run_steps(g0, count, n, 0, n, N, 1.0 / n, 1e-4, 1e-3, 1, stream)
 
-        forms = [("two_launch", 0, 1, 0, 0)] + [
-            (f"xstep_bar{b}_pf{q}" + (f"_pix{px}" if px else ""), -1, b, q, px)
-            for b in a.bar for q in a.pf for px in a.pix if (b == 1 or q == 0) and (b == 3 or px == 0)]
+        forms = [("two_launch", 0, 0)] + [("xstep" + (f"_pix{px}" if px else ""), -1, px) for px in a.pix]
         if a.rm:
-            forms.append(("xstep_rm", -1, 3, 0, 0))
+            forms.append(("xstep_rm", -1, 0))
         dz0 = st.dz_swz
         for rnd in range(a.rounds):
-            for name, xs, b, q, px in forms:
-                st.xstep, st.xstep_bar, st.xstep_pf, st.xstep_pix = xs, b, q, px
+            for name, xs, px in forms:
+                st.xstep, st.xstep_pix = xs, px
                 st.dz_swz = 0 if name == "xstep_rm" else dz0
                 walk(20)
                 torch.cuda.synchronize()
@@ -100,7 +100,7 @@ def main(argv=None):
             # into the step on any XCD): per XCD, medians over its workers (and the role workgroup)
             k = a.stamps
             buf = torch.zeros(k * 8 * 32 * 4, dtype=torch.int64, device="cuda")
-            st.xstep, st.xstep_bar, st.xstep_pf = -1, a.bar[-1], a.pf[-1]
+            st.xstep = -1
             st.xs_stamps, st.xs_stamp_steps = buf.data_ptr(), k
             walk(k)
             torch.cuda.synchronize()
@@ -119,7 +119,7 @@ def main(argv=None):
                            "dw1_done_last": np.median(w[:, :, 3].max(axis=1)), "role_done": np.median(r[:, 3])}
                 rows[x] = {kk: round(float(v) / 100, 3) for kk, v in rows[x].items()}
             per = np.diff(g0[:, 0]) / 100
-            emit({"n": n, "H": a.hidden, "bar": a.bar[-1], "stamps_steps": k, "step_period_median_us": round(float(np.median(per)), 3),
+            emit({"n": n, "H": a.hidden, "stamps_steps": k, "step_period_median_us": round(float(np.median(per)), 3),
                   "per_xcd_median_us_from_step_start": rows})
         if a.w1_stamps:
             # the dW1 tiles' per-wave stamps of the LAST step of a K-step plan (the diagnostics build; XStepPlan::
@@ -129,7 +129,7 @@ def main(argv=None):
             k = a.w1_stamps
             for px in a.pix:
                 buf = torch.zeros(256 * 8 * 6, dtype=torch.int64, device="cuda")
-                st.xstep, st.xstep_bar, st.xstep_pf, st.xstep_pix = -1, 3, 0, px
+                st.xstep, st.xstep_pix = -1, px
                 st.xs_w1stamps = buf.data_ptr()
                 walk(k)
                 torch.cuda.synchronize()
@@ -153,7 +153,7 @@ def main(argv=None):
             k = a.fha_stamps
             fst = torch.zeros(2 * 256 * 4, dtype=torch.int64, device="cuda")
             hst = torch.zeros(256 * 8 * 4, dtype=torch.int64, device="cuda")
-            st.xstep, st.xstep_bar, st.xstep_pf = -1, a.bar[-1], a.pf[-1]
+            st.xstep = -1
             st.stamps, st.hstamps = fst.data_ptr(), hst.data_ptr() if a.gemm_stamps else 0
             walk(k)
             torch.cuda.synchronize()
@@ -181,7 +181,7 @@ def main(argv=None):
                                   "published": round(float(np.median(f4[m, 1] - t0)) / 100, 3),
                                   "gathered": round(float(np.median(f4[m, 2] - t0)) / 100, 3),
                                   "end": round(float(np.median(f4[m, 3] - t0)) / 100, 3)}
-            emit({"n": n, "H": a.hidden, "bar": st.xstep_bar, "fha_stamps_last_of": k,
+            emit({"n": n, "H": a.hidden, "fha_stamps_last_of": k,
                   "fha_median_us": {kk: (round(float(v) / 100, 3) if v is not None else None) for kk, v in rows.items()},
                   "fha_per_xcd_median_us": per_xcd})
     if out:

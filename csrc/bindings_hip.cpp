@@ -191,8 +191,6 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       .def_readwrite("xp_dbg", &MlpStep::xp_dbg)
       .def_readwrite("g64_touch", &MlpStep::g64_touch)
       .def_readwrite("xstep", &MlpStep::xstep)
-      .def_readwrite("xstep_bar", &MlpStep::xstep_bar)
-      .def_readwrite("xstep_pf", &MlpStep::xstep_pf)
       .def_readwrite("xstep_pix", &MlpStep::xstep_pix)
       .def_readonly("xstep_used", &MlpStep::xstep_used)
       .def_readonly("xstep_reason", &MlpStep::xstep_reason)

@@ -15,9 +15,11 @@
 // follows reads *err and applies nothing (SplitStepArgs::ag_err; MlpEngine.kernel_error(), KernelHandoffTimeout).
 //
 // PS (the XCD-local step pipeline, xstep.hip): the same body as one phase of a persistent multi-step launch -- the
-// caller names the tile (rt, ct) and the step's granule tag, and the operands other workgroups of that launch rewrite
-// between steps (b1, W2, b2; W1s in the K loop) are read with sc1 (L1-bypassing) loads; every row tile stores D
-// (h.D: its own XCD's copy).  Returns false when a hand-off wait timed out (nothing after it was written).
+// caller names the tile (rt, ct) and the step's granule tag; each GEMM wave first waits on its XCD's flag line for the
+// previous step's updates it reads (PsGate), and the operands other workgroups of that launch rewrite between steps
+// (b1, W2, b2, staged into LDS by wave 7: EpiSigGate; W1s in the K loop) are read with sc1 (L1-bypassing) loads;
+// every row tile stores D (h.D: its own XCD's copy).  Returns false when a wait timed out or the launch stopped
+// (nothing after it was written).
 #pragma once
 
 #include "fwd_tile.h"
@@ -34,8 +36,7 @@ constexpr int kAgCounterStride = 32;  // uint64 words: one 256-byte line per til
 
 __device__ __forceinline__ float ag_sigmoid(float x) { return sigmoid_f32(x); }  // (head_math.h)
 
-template <int CP = 0>  // CP: the b1 load's cache policy (kSc1 under PS)
-struct EpiSigLdsT {
+struct EpiSigLds {
   const float* b1;
   float* a1;
   float (*a1s)[33];  // [16][32 + 1] this workgroup's a1 tile
@@ -43,7 +44,7 @@ struct EpiSigLdsT {
   float xscale;
   float pre[kEpiMaxQ];
   __device__ __forceinline__ void prefetch(int q, int row, int, bool ok) {
-    pre[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(make_rsrc(b1), ok ? row * 4 : kOOB, 0, CP));
+    pre[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(make_rsrc(b1), ok ? row * 4 : kOOB, 0, 0));
   }
   __device__ __forceinline__ void operator()(int q, int row, int col, float v) {
     const float s = ag_sigmoid(v * xscale + pre[q]);
@@ -53,53 +54,56 @@ struct EpiSigLdsT {
   }
 };
 
-// ---- the XCD-local step pipeline's flag line (xstep.hip XsBar): one 32-bit word per participant of an XCD in one
-// 128-byte line of that XCD's L2, word 31 the launch's stop word.  ONE WAVE (every lane) waits until the words of
-// participants [lo, hi) -- and `extra` when >= 0 -- carry `tag` (wrap-safe >=).  False when the launch stops: the
-// stop word, or a wait past limit_us (then *err is set and the stop word written); *s_stop (LDS) is set either way.
-__device__ __forceinline__ bool xcd_flags_wait(unsigned* line, unsigned tag, unsigned stop_tag, int lo, int hi,
-                                               int extra, int* s_stop, int* err, uint32_t limit_us) {
-  const int l = threadIdx.x & 63;
-  const __amdgpu_buffer_rsrc_t rl = make_rsrc(line);
-  const uint64_t limit = (uint64_t)limit_us * kTicksPerUs;
-  uint64_t t0 = 0;
-  for (uint32_t pass = 1;; ++pass) {
-    const unsigned v = __builtin_amdgcn_raw_buffer_load_b32(rl, l < 32 ? l * 4 : kOOB, 0, kSc1);
-    if (__any(l == 31 && v == stop_tag)) {
-      if (l == 0) *s_stop = 1;
-      return false;
-    }
-    if (__all(!((l >= lo && l < hi) || l == extra) || v - tag < 0x80000000u)) return true;
-    if (pass == 1) t0 = wall_ticks();
-    else if ((pass & 7) == 0 && wall_ticks() - t0 > limit) {
-      if (l == 0) {
-        atomicExch(err, 1);
-        line[31] = stop_tag;
-        *s_stop = 1;
+// ---- the XCD-local step pipeline's flag line (xstep.hip): one 32-bit word per participant of an XCD in one 128-byte
+// line of that XCD's L2, each holding the tag of the participant's last arrival; word 31 is the launch's stop word.
+struct XcdFlags {
+  unsigned* line = nullptr;
+  unsigned stop_tag = 0;  // word 31 holds it once this launch has stopped
+  int* s_stop = nullptr;  // the waiting workgroup's stop mark (LDS)
+  int* err = nullptr;
+  uint32_t limit_us = 0;
+  // ONE WAVE (every lane) waits until the words of participants [lo, hi) -- and `extra` when >= 0 -- carry `tag`
+  // (wrap-safe >=).  False when the launch stops: the stop word, or a wait past limit_us (then *err is set and the
+  // stop word written); *s_stop is set either way.
+  __device__ __forceinline__ bool wait(unsigned tag, int lo, int hi, int extra = -1) const {
+    const int l = threadIdx.x & 63;
+    const __amdgpu_buffer_rsrc_t rl = make_rsrc(line);
+    const uint64_t limit = (uint64_t)limit_us * kTicksPerUs;
+    uint64_t t0 = 0;
+    for (uint32_t pass = 1;; ++pass) {
+      const unsigned v = __builtin_amdgcn_raw_buffer_load_b32(rl, l < 32 ? l * 4 : kOOB, 0, kSc1);
+      if (__any(l == 31 && v == stop_tag)) {
+        if (l == 0) *s_stop = 1;
+        return false;
       }
-      return false;
+      if (__all(!((l >= lo && l < hi) || l == extra) || v - tag < 0x80000000u)) return true;
+      if (pass == 1) t0 = wall_ticks();
+      else if ((pass & 7) == 0 && wall_ticks() - t0 > limit) {
+        if (l == 0) {
+          atomicExch(err, 1);
+          line[31] = stop_tag;
+          *s_stop = 1;
+        }
+        return false;
+      }
+      __builtin_amdgcn_s_sleep(1);
     }
-    __builtin_amdgcn_s_sleep(1);
   }
-}
+};
 
-// PS with a gate (PSG): instead of a barrier between the previous step's weight update and this forward, each wave
+// The PS forward's gate: instead of a barrier between the previous step's weight update and this forward, each wave
 // of the forward GEMM waits for the flags of the dW1 tiles that wrote the W1 columns of its K range (dW1 feature tile
 // j = features [32 j, 32 j + 32)); the wave with no K range (wave 7) waits for every dW1 tile and the role workgroup
 // -- this step's head then overwrites what they read (dZ1, D, the dW2 partials) -- and then stages b1 (this tile's
-// rows), W2[:, rows] and b2 into LDS for the epilogue and the head (nobody else loads them).  line == nullptr: the
-// plan's first step, nothing to wait for.
+// rows), W2[:, rows] and b2 into LDS for the epilogue and the head (nobody else loads them).
 struct PsGate {
-  unsigned* line = nullptr;
-  unsigned tag = 0, stop_tag = 0;  // the previous step's second-barrier tag, this launch's stop value
-  int ntiles = 0, role = 0;        // dW1 tiles of the XCD (slots [0, ntiles)), the role's slot
-  int* s_stop = nullptr;
-  int* err = nullptr;
-  uint32_t limit_us = 0;
+  const XcdFlags* flags = nullptr;  // the XCD's line (nullptr: the plan's first step, nothing to wait for)
+  unsigned tag = 0;          // the previous step's second arrival
+  int ntiles = 0, role = 0;  // dW1 tiles of the XCD (slots [0, ntiles)), the role's slot
 };
 
 template <int CP, bool A1 = false>
-struct EpiSigGate {  // (EpiSigLdsT's arithmetic; b1 from LDS, staged by wave 7; A1: the a1 store's test compiled in)
+struct EpiSigGate {  // (EpiSigLds's arithmetic; b1 from LDS, staged by wave 7; A1: the a1 store's test compiled in)
   float* a1;
   float (*a1s)[33];
   int ld, r0, c0;
@@ -114,11 +118,10 @@ struct EpiSigGate {  // (EpiSigLdsT's arithmetic; b1 from LDS, staged by wave 7;
   __device__ void before_kloop(int kbeg, int kend) {
     const PsGate& g = *gate;
     if (kend > kbeg) {
-      if (g.line) xcd_flags_wait(g.line, g.tag, g.stop_tag, kbeg / 32, min(g.ntiles, (kend + 31) / 32), -1, g.s_stop,
-                                 g.err, g.limit_us);
+      if (g.flags) g.flags->wait(g.tag, kbeg / 32, min(g.ntiles, (kend + 31) / 32));
       return;
     }
-    if (g.line) xcd_flags_wait(g.line, g.tag, g.stop_tag, 0, g.ntiles, g.role, g.s_stop, g.err, g.limit_us);
+    if (g.flags) g.flags->wait(g.tag, 0, g.ntiles, g.role);
     const int l = threadIdx.x & 63;
     if (l < 16)
       b1s[l] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(make_rsrc(b1), r0 + l < H ? (r0 + l) * 4 : kOOB,
@@ -143,17 +146,19 @@ struct EpiSigGate {  // (EpiSigLdsT's arithmetic; b1 from LDS, staged by wave 7;
 
 // blk: the workgroup's slot in the XCD-grouped grid (the hardware XCD is blk & 7).  red: >= 8 * 2 * 4 * 64
 // floats of LDS.
+// ps_gate, ps_stop (PS only): the step's gate and the workgroup's stop mark in LDS, which a flag wait that saw the
+// launch stop has set by the time the GEMM returns.
 // DG (PS only): the diagnostics build -- the stamps and the hand-off test hook (SplitStepArgs::ag_test_skip); a
 // production PS body compiles neither, nor the a1 store and the loss partials (the pipeline takes neither: mlp_xstep_ok)
 // HK (PS only): the non-PS body's runtime tests kept in the build -- bit 0 the hand-off hook, bit 1 the loss
 // partials, bit 2 the a1 store; each is a no-op in the pipeline (mlp_xstep_ok), but with all three the compiler's
 // schedule of the body is 0.25 us faster per step (xstep.hip's launcher, profiles/r6/hk/)
-template <int NPW, int VEC, bool AF, int SWZ = 0, bool PS = false, bool PSG = false, bool DG = !PS, int HK = 0>
+template <int NPW, int VEC, bool AF, int SWZ = 0, bool PS = false, bool DG = !PS, int HK = 0>
 __device__ __forceinline__ bool fha_body(const SplitStepArgs& f, const HeadArgs& h,
                                          unsigned long long* __restrict__ counters, gran_t* __restrict__ slabs,
                                          int* __restrict__ err, int tm, int tn, int blk, float* red, int ps_rt = 0,
-                                         int ps_ct = 0, unsigned ps_ep = 0, const PsGate* ps_gate = nullptr) {
-  static_assert(!PSG || PS, "the gate is a persistent-pipeline form");
+                                         int ps_ct = 0, unsigned ps_ep = 0, const PsGate* ps_gate = nullptr,
+                                         const int* ps_stop = nullptr) {
   constexpr int CP = PS ? kSc1 : 0;
   constexpr int kCols = 32;
   __shared__ float a1s[16][kCols + 1];
@@ -235,22 +240,22 @@ __device__ __forceinline__ bool fha_body(const SplitStepArgs& f, const HeadArgs&
   // trip in front of the GEMM, ~0.5 us of the launch per bench/stamps_fha.py)
   const int wc = t >> 4, wr = t & 15;
   TileGeom g{H, n, f.P, r0, c0};
-  if constexpr (PSG) {  // (wave 7 stages b1, W2 and b2 into LDS inside the GEMM, after its wait: EpiSigGate)
+  if constexpr (PS) {  // (wave 7 stages b1, W2 and b2 into LDS inside the GEMM, after its wait: EpiSigGate)
     __shared__ float b1s[16];
     EpiSigGate<CP, (HK & 4) != 0> epi{f.a1, a1s, f.ld, r0, c0, f.xscale, ps_gate, b1s, w2s, b2s, f.b1, static_cast<const float*>(h.W2),
                        static_cast<const float*>(h.b2), H, C};
     fwd_tile<NPW, 2, VEC, 4, AF, SWZ, CP>(f, g, epi, red, kStamps ? h.stamps : nullptr);
     stamp2(0);
-    if (*ps_gate->s_stop) {  // (a wait of this step's gate saw the launch stop: nothing is written)
+    if (*ps_stop) {  // (a wait of this step's gate saw the launch stop: nothing is written)
       stamps_out();
       return false;
     }
   } else {
     const float w2v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-        make_rsrc(h.W2), (t < 256 && wc < C && r0 + wr < H) ? (wc * H + r0 + wr) * 4 : kOOB, 0, CP));
+        make_rsrc(h.W2), (t < 256 && wc < C && r0 + wr < H) ? (wc * H + r0 + wr) * 4 : kOOB, 0, 0));
     const float b2v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-        make_rsrc(h.b2), (t >= 256 && t < 256 + 16 && t - 256 < C) ? (t - 256) * 4 : kOOB, 0, CP));
-    EpiSigLdsT<CP> epi{f.b1, f.a1, a1s, f.ld, r0, c0, f.xscale, {}};
+        make_rsrc(h.b2), (t >= 256 && t < 256 + 16 && t - 256 < C) ? (t - 256) * 4 : kOOB, 0, 0));
+    EpiSigLds epi{f.b1, f.a1, a1s, f.ld, r0, c0, f.xscale, {}};
     fwd_tile<NPW, 2, VEC, 4, AF, SWZ, CP>(f, g, epi, red, kStamps ? h.stamps : nullptr);  // (per-wave GEMM timeline)
     stamp2(0);
     // wsk_tile ends with a barrier: a1s is complete.  Rows past H / columns past n: a1s holds stale LDS, so

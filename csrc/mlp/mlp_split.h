@@ -232,8 +232,8 @@ int mlp_fwd1_wide_ag(const SplitStepArgs& a, const HeadArgs& h, unsigned long lo
 void mlp_split_wgrad(const SplitStepArgs& a, hipStream_t s);
 
 // The XCD-local step pipeline (xstep.hip): every step of a native step-loop plan (MlpStep::run_steps) in ONE
-// persistent launch -- row tile rt's forward + head, dW1 tiles and W2 rows on XCD rt, two XCD-local barriers per step,
-// the z2 all-gather the only cross-XCD hand-off.  `a` / `h` are the plan's step as the two-launch form would run it
+// persistent launch -- row tile rt's forward + head, dW1 tiles and W2 rows on XCD rt, ordered by per-wave waits on the
+// XCD's flag line (no barrier across workgroups), the z2 all-gather the only cross-XCD hand-off.  `a` / `h` are the plan's step as the two-launch form would run it
 // (fragment-ordered W1, pixels and dZ1 -- or, a.dz_swz == 0, row-major pixels and fp32 dZ1 for steps off the
 // 16-sample grid such as n = 100 -- the head's dW2 partials, fused SGD; their pixel / label pointers are re-based per
 // step from the plan's bases).
@@ -248,22 +248,16 @@ struct XStepPlan {
   unsigned ep0 = 1;        // the first step's granule tag; step s uses ep0 + s (tags never repeat over a buffer's life)
   unsigned launch = 0;     // launches so far: control bank launch & 1
   unsigned long long* gran = nullptr;  // z2 partial granules [2 step parities][32][8][16][32]
-  unsigned long long* ctl = nullptr;   // [2 banks][8 XCDs][64] ticket / barrier words, zeroed once at allocation
+  unsigned long long* ctl = nullptr;   // kXstepCtlWords: the tickets and flag lines, zeroed once at allocation
   float* Dx = nullptr;     // [8 XCDs][16][ld]: each XCD's copy of D (its role workgroup's db2 reads it)
   float* b2x = nullptr;    // [8 XCDs][16]: each XCD's copy of b2 (updated in the same order on every XCD)
   int* err = nullptr;      // the sticky timed-out word (MlpEngine.ag_err)
   int nw = 0;              // workers per XCD (mlp_xstep_workers)
-  int npf = 0;             // prefetch workgroups per XCD (idle CUs pulling the pixels the XCD reads next into its L2)
-  int bar = 3;             // the XCD-local barriers: 0 an atomic counter, 1 a flag line in the XCD's L2 (xstep.hip XsBar),
-                           // 2 the flag line with the first barrier fine-grained (each dW1 wave waits for its own
-                           // column tiles' dZ1: EpiW1Gate), 3 both fine-grained (the next step's forward waves wait
-                           // for their own dW1 tiles, wave 7 for all of them and the role: fha_body PsGate)
-                           // -- n = 800 walking step: 0 ~14, 1 11.0, 2 10.8, 3 9.85 us (profiles/r6/xstep_ab_r6i.jsonl)
-  int pix = 1;             // the dW1 tiles' pixel operand (fragment-ordered form, bar 3): 0 the feature-major copy XT0,
+  int pix = 1;             // the dW1 tiles' pixel operand (fragment-ordered form): 0 the feature-major copy XT0,
                            // 1 the forward's copy Xs0 out of the XCD's L2, transposed through LDS (xstep.hip PIX)
   unsigned long long* stamps = nullptr;  // diagnostics: [stamp_steps][8][32][4] s_memrealtime per workgroup
   int stamp_steps = 0;
-  // diagnostics (barrier form 3): the dW1 tiles' per-wave stamps of the plan's LAST step, by launch workgroup --
+  // diagnostics: the dW1 tiles' per-wave stamps of the plan's LAST step, by launch workgroup --
   // [256][8 waves][4]: tile entered, K loop done, reduced, epilogue done; then [256][8][2]: gate passed, the first
   // burst's operands back
   unsigned long long* w1stamps = nullptr;
@@ -274,7 +268,9 @@ int mlp_xstep_rm(const SplitStepArgs& a);  // the row-major form's dW1 vector fo
 int mlp_xstep_workers(const SplitStepArgs& a);
 void mlp_xstep(const SplitStepArgs& a, const HeadArgs& h, const XStepPlan& p, hipStream_t s);
 constexpr int64_t kXstepGranules = 2 * 32 * 8 * 16 * 32;
-constexpr int64_t kXstepCtlWords = 2 * 8 * 64 + 8 * 16;
+// [2 banks][8 XCDs][32] ticket words, then [8 XCDs][16] flag lines (xstep.hip xs_ticket / xs_flags; the barrier
+// counters that shared the ticket's 512 bytes went with the counter barrier, so a ticket keeps one 256-byte line)
+constexpr int64_t kXstepCtlWords = 2 * 8 * 32 + 8 * 16;
 
 // planes[p][i] for i < n: exact np-way bf16 split of W[i] (np = 1: plain rounding).
 void mlp_split_planes(const float* W, void* planes, int64_t n, int np, hipStream_t s);

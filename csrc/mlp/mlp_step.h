@@ -150,8 +150,8 @@ struct MlpStep {
   // The XCD-local step pipeline (mlp_xstep, csrc/mlp/xstep.hip): run_steps runs the whole plan in ONE persistent
   // launch when the plan's step has the pipeline's shape (H <= 128 split3, fragment-ordered operands, the head's dW2
   // partials, fused SGD, one process, steps on the 16-sample grid); -1 auto (on), 0 off, 1 required (an error if
-  // the plan does not qualify).  xstep_bar: XStepPlan::bar (the XCD-local barrier's form).
-  int xstep = -1, xstep_bar = 3, xstep_pf = 0;  // xstep_pf: XStepPlan::npf
+  // the plan does not qualify).
+  int xstep = -1;
   int xstep_pix = 1;      // XStepPlan::pix: the dW1 tiles' pixel operand (0 XT, 1 the forward's copy through LDS)
   int xstep_used = 0;     // the last run_steps ran as one xstep launch (tests, bench records)
   std::string xstep_reason = "";  // why the last run_steps did not take the pipeline ("" when it did)

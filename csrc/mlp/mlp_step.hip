@@ -326,7 +326,6 @@ const char* MlpStep::plan_steps(int64_t gstart0, int64_t count, int64_t B, int64
   if (!p.f.w1_swz || mlp_split_w1_planes_read(p.f)) return "the forward would not read fp32 W1";
   if (!p.w.dz_swz) {  // the pipeline's row-major form
     if (xs_stamps || xs_w1stamps || hstamps || ag_test_skip >= 0) return "the row-major form has no diagnostics build";
-    if (xstep_bar != 3 || xstep_pf != 0) return "the row-major form exists in barrier form 3 only";
     if (!mlp_xstep_rm(p.w)) return "the row-major form needs n % 4 == 0 and 4-byte aligned pixel columns";
   }
   if (p.fwd != StepForm::kAllGather) return "the all-gather head does not fit";
@@ -361,9 +360,7 @@ bool MlpStep::run_xstep(int64_t gstart0, int64_t count, int64_t B, int64_t shard
   p.ep0 = xs_ep; p.launch = xs_launch;
   p.gran = xs_gran; p.ctl = xs_ctl; p.Dx = xs_dx; p.b2x = xs_b2x; p.err = P_<int>(ag_err);
   p.nw = mlp_xstep_workers(f.w);
-  p.bar = xstep_bar;
   p.pix = xstep_pix;
-  p.npf = std::max(0, std::min(xstep_pf, 32 - p.nw - 1));
   p.stamps = reinterpret_cast<unsigned long long*>(xs_stamps);
   p.stamp_steps = xs_stamps ? xs_stamp_steps : 0;
   p.w1stamps = reinterpret_cast<unsigned long long*>(xs_w1stamps);

@@ -14,41 +14,48 @@
 //     workgroups that read the same XCC id, i.e. that share one L2);
 //   * slot j < nw is a worker: the forward + head of tile (rt, column tile j) -- fha_body, the two-launch forward's
 //     own body, in its PS form: z2 partials out as data-tagged granules (tag = the plan's step number, slab by step
-//     parity), the all-gather, softmax, D, the dW2 partials and dZ1 -- then, after the XCD's first barrier, the dW1
-//     tile (rt, feature tile j) over the whole batch with the fused reg + SGD update of W1 / W1s / b1 (EpiW1, the
-//     two-launch epilogue) -- its pixel operand out of the forward's fragment-ordered copy, which this XCD's L2 holds,
-//     not the feature-major copy (PIX below);
-//   * slot nw is the XCD's role workgroup: after the first barrier it sums the dW2 partials of W2[:, rt rows] (EpiW2)
-//     and reduces D into db2 -- redundantly on every XCD, in the same order, into that XCD's own copy of b2 (XCD 0
-//     also writes the master b2 at the plan's last step);
-//   * the other slots idle.  (Extra workgroups pulling the pixels each XCD reads next into its L2 -- this step's XT,
+//     parity), the all-gather, softmax, D, the dW2 partials and dZ1 -- then, each wave once the column tiles it reads
+//     have arrived, the dW1 tile (rt, feature tile j) over the whole batch with the fused reg + SGD update of W1 /
+//     W1s / b1 (EpiW1, the two-launch epilogue) -- its pixel operand out of the forward's fragment-ordered copy, which
+//     this XCD's L2 holds, not the feature-major copy (PIX below);
+//   * slot nw is the XCD's role workgroup: once every column tile has arrived it sums the dW2 partials of
+//     W2[:, rt rows] (EpiW2) and reduces D into db2 -- redundantly on every XCD, in the same order, into that XCD's own
+//     copy of b2 (XCD 0 also writes the master b2 at the plan's last step);
+//   * the other slots return at once.  (Idle CUs pulling the pixels each XCD reads next into its L2 -- this step's XT,
 //     the next step's X -- measured slower, +1.5 us per step, and so did the workers' own LDS-DMA pull during the z2
 //     wait and an LDS-DMA of the dW1 tile's pixels ahead of its GEMM (the DMAs share the in-order vmcnt with the
 //     critical loads): profiles/r6/xstep_ab_r6b.jsonl, xstep_ab_r6c_prefetch_rejected.jsonl, xpf_rejected/.)
 //
-// Synchronisation is XCD-local (XsBar), in four forms (XStepPlan::bar; the default, 3, has no full barrier left):
-// each participant drains its stores (s_waitcnt vmcnt(0) + workgroup barrier) and signals on its XCD's flag line (one
-// 128-byte line, a plain-store tag per slot) or counter; in form 3 each dW1 wave waits only for the column tiles its
-// K range reads (EpiW1Gate) and each forward wave of the next step only for the dW1 tiles its K range reads (fha_body
-// PsGate; its wave 7, which has no K range, waits for all of them and the role and stages b1 / W2 / b2).  Every read
-// of data another workgroup of the launch wrote goes through sc1 (L1-bypassing, L2-served) loads, so a CU never reuses
-// a stale L1 line, and the producer's plain stores stay in the XCD's L2 (bench/micro/xcd_barrier.hip: the same-XCD
-// read-back checked word by word, and priced, profiles/r6/xcd_barrier_micro*.jsonl).  Arithmetic and summation
-// orders are those of the two-launch step, so the parameters are bitwise equal to it (tests/test_gpu_xstep.py).
+// Synchronisation is XCD-local and has no barrier across workgroups, only the XCD's FLAG LINE (fha_body.h XcdFlags,
+// XsBar below): one 32-bit word per slot in a single 128-byte line, written with a PLAIN store -- the line stays in
+// this XCD's L2, no trip to the memory-side atomic unit -- holding the tag of the slot's last arrival, 2 (ep0 + s) + b
+// for arrival b of step s (tags only grow over the buffer's life, so nothing is ever reset).  Word 31 is the stop word:
+// launch + 1 once this launch has stopped.  Valid because every participant of a line is on the XCD whose L2 holds it
+// (they all read the same XCC id).  A workgroup arrives twice per step, after its forward + head (b = 0) and after its
+// dW1 tile or role (b = 1): it drains its stores (s_waitcnt vmcnt(0) + workgroup barrier) and writes its word.  A
+// waiter is one wave polling the line with sc1 loads for just the words it depends on: each dW1 wave the column tiles
+// its K range reads (EpiW1Gate), the role every column tile, and each forward wave of the next step the dW1 tiles its
+// K range reads (fha_body PsGate; its wave 7, which has no K range, waits for all of them and the role and stages
+// b1 / W2 / b2).  (Two full XCD barriers per step on the same line measured 11.0 us per walking step at n = 800, only
+// the first of them fine-grained 10.8, this form 9.85, and an atomic counter per XCD in place of the line ~14:
+// profiles/r6/xstep_ab_r6i.jsonl.)  Every read of data another workgroup of the launch wrote goes through sc1
+// (L1-bypassing, L2-served) loads, so a CU never reuses a stale L1 line, and the producer's plain stores stay in the
+// XCD's L2 (bench/micro/xcd_barrier.hip: the same-XCD read-back checked word by word, and priced,
+// profiles/r6/xcd_barrier_micro*.jsonl).  Arithmetic and summation orders are those of the two-launch step, so the
+// parameters are bitwise equal to it (tests/test_gpu_xstep.py).
 // Walking step at n = 800: 9.4-9.5 us against the two-launch loop's 14.0 (profiles/r6/flags/, docs/ROUND6_STATUS.md);
 // n = 100 (the row-major form, RM below): 8.90 us against 12.33 (profiles/r6/rm_form/).
 //
 // Failure semantics: a z2 hand-off wait that outlasts SplitStepArgs::ag_wait_us sets *err and makes its workgroup
-// arrive "bad" at the first barrier; every XCD's workgroup of that column tile waits for the same missing granule,
-// so every XCD stops there and the step applies nothing (the launch ends; the steps before it stay applied).  A
-// barrier wait that times out (a workgroup that never arrives) sets *err and stops the launch.
+// arrive "bad" (it writes the stop word first); every XCD's workgroup of that column tile waits for the same missing
+// granule, so every XCD stops there and the step applies nothing (the launch ends; the steps before it stay applied).
+// A flag wait that times out (a workgroup that never arrives) sets *err and stops the launch.
 // Reference: the hot loop of fpcode/neural_network.cpp:449-555 (forward/backward :281-394) -- here one launch.
 #include "mlp_split.h"
 #include "mlp_kernels.h"
 
 #include "fha_body.h"
 #include "granule.h"
-#include "l2_touch.h"
 #include "mma_tile.h"
 #include "wgrad_epi.h"
 
@@ -60,7 +67,6 @@ using bf16 = __hip_bfloat16;
 using namespace wg;
 
 constexpr int kXsWgsPerXcd = 32;                 // 256 CUs / 8 XCDs: one workgroup per CU
-constexpr unsigned long long kXsBad = 1ull << 40;  // a barrier arrival that stops the XCD (added to the count)
 constexpr int kXsCols = 32;                      // the forward's column tile (fha_body)
 
 inline int xs_cdiv(int a, int b) { return (a + b - 1) / b; }
@@ -71,131 +77,49 @@ __device__ __forceinline__ unsigned xcc_id() {
   return v & 15u;
 }
 
-// control words: [2 banks][8 XCDs][64] uint64 -- ticket at [0], barrier counter at [32] (separate 256-byte lines)
+// control words: [2 banks][8 XCDs][32] uint64 -- the XCD's ticket at [0] (one 256-byte line each; the launch that
+// takes ticket 0 of its bank zeroes the other bank's, for the next launch) ...
 __device__ __forceinline__ unsigned long long* xs_ticket(unsigned long long* ctl, int bank, int x) {
-  return ctl + ((size_t)bank * 8 + x) * 64;
+  return ctl + ((size_t)bank * 8 + x) * 32;
 }
-__device__ __forceinline__ unsigned long long* xs_counter(unsigned long long* ctl, int bank, int x) {
-  return ctl + ((size_t)bank * 8 + x) * 64 + 32;
-}
-// ... then [8 XCDs][16] uint64: one 128-byte flag line per XCD (XsBar<1>), never reset
+// ... then [8 XCDs][16] uint64: one 128-byte flag line per XCD, never reset
 __device__ __forceinline__ unsigned* xs_flags(unsigned long long* ctl, int x) {
-  return reinterpret_cast<unsigned*>(ctl + 2 * 8 * 64 + (size_t)x * 16);
+  return reinterpret_cast<unsigned*>(ctl + 2 * 8 * 32 + (size_t)x * 16);
 }
 
-// The XCD-local barriers.  Every participant first drains its stores (s_waitcnt vmcnt(0) in every wave, then a
-// workgroup barrier); lane 0 then signals and wave 0 waits; the other waves wait at a workgroup barrier.  sync(q, bad)
-// is the plan's q-th barrier (two per step: q = 2 s + b); false (block-uniform) when the XCD must stop -- a bad
-// arrival (a timed-out z2 hand-off upstream) or a wait past `limit_us` (then *err is set and the stop is signalled
-// to every other waiter).
-//
-// BAR 0: one monotonic 64-bit counter per XCD (ctl bank launch & 1), an agent-scope atomic add per arrival, lane 0
-//        polling it with sc1 loads (bench/micro/xcd_barrier.hip mode 2: 0.64 us from arrival to release); a stop
-//        adds kXsBad.
-// BAR 1: a FLAG LINE per XCD: one 32-bit word per participant in a single 128-byte line, written with a PLAIN
-//        store -- the line stays in this XCD's L2, no trip to the memory-side atomic unit -- holding the barrier's tag
-//        2 (ep0 + s) + b (tags only grow over the buffer's life, so nothing is ever reset); lanes 0-31 of wave 0 poll
-//        the whole line with sc1 (L2-served) loads.  Word 31 is the stop word: launch + 1 when this launch stopped.
-//        Valid because every participant of a line is on the XCD whose L2 holds it (they all read the same XCC id).
-template <int BAR>
+// One workgroup's end of its XCD's flag line: arrival q of the plan is 2 s + b (step s, b = 0 after the forward +
+// head, 1 after the dW1 tile / the role).
 struct XsBar {
-  unsigned long long* cnt;  // BAR 0
-  unsigned* line;           // BAR 1: 32 words
-  unsigned long long np;    // participants
-  unsigned ep0, stop_tag;   // BAR 1: the first step's granule tag, this launch's stop value
+  XcdFlags flags;
+  unsigned ep0;  // the first step's granule tag
   int slot;
-  int* err;
-  uint32_t limit_us;
-  int* s_stop;
   __device__ unsigned tag_of(int q) const { return 2u * (ep0 + (unsigned)(q >> 1)) + (unsigned)(q & 1); }
-  // BAR 1: this workgroup's stores drained (every wave), then lane 0 publishes its flag (and the stop word first when
-  // its step is bad).  Returns after the workgroup barrier that follows the drain: the flag may still be in flight.
+  // this workgroup's stores drained (every wave), then lane 0 publishes its flag (and the stop word first when its
+  // step is bad).  Returns after the workgroup barrier that follows the drain: the flag may still be in flight.
   __device__ void arrive(int q, bool bad) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
-      if (bad) line[31] = stop_tag;
-      line[slot] = tag_of(q);
+      if (bad) flags.line[31] = flags.stop_tag;
+      flags.line[slot] = tag_of(q);
     }
   }
-  // BAR 1, one WAVE (all its lanes): wait until the flags of participants [lo, hi) carry barrier q's tag.  False when
-  // the launch stops (the stop word, or a wait past limit_us: then *err is set and the stop word written); *s_stop is
-  // then set for the workgroup (read after its next workgroup barrier).
-  __device__ bool poll(int q, int lo, int hi) {
-    const int l = threadIdx.x & 63;
-    const unsigned tag = tag_of(q);
-    const __amdgpu_buffer_rsrc_t rl = make_rsrc(line);
-    const uint64_t limit = (uint64_t)limit_us * kTicksPerUs;
-    uint64_t t0 = 0;
-    for (uint32_t pass = 1;; ++pass) {
-      const unsigned v = __builtin_amdgcn_raw_buffer_load_b32(rl, l < 32 ? l * 4 : kOOB, 0, kSc1);
-      if (__any(l == 31 && v == stop_tag)) {
-        if (l == 0) *s_stop = 1;
-        return false;
-      }
-      if (__all(l < lo || l >= hi || v - tag < 0x80000000u)) return true;  // (wrap-safe v >= tag)
-      if (pass == 1) t0 = wall_ticks();
-      else if ((pass & 7) == 0 && wall_ticks() - t0 > limit) {
-        if (l == 0) {
-          atomicExch(err, 1);
-          line[31] = stop_tag;
-          *s_stop = 1;
-        }
-        return false;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-  }
-  // the whole barrier: arrive, wave 0 waits for every participant, the workgroup joins it
-  __device__ bool sync(int q, bool bad) {
-    const int t = threadIdx.x;
-    if constexpr (BAR == 0) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      const uint64_t limit = (uint64_t)limit_us * kTicksPerUs;
-      if (t == 0) {
-        const unsigned long long target = (unsigned long long)(q + 1) * np;
-        __hip_atomic_fetch_add(cnt, bad ? 1ull + kXsBad : 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint64_t t0 = 0;
-        for (uint32_t pass = 1;; ++pass) {
-          const unsigned long long v = __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (v >= kXsBad) {
-            *s_stop = 1;
-            break;
-          }
-          if (v >= target) break;
-          if (pass == 1) t0 = wall_ticks();
-          else if ((pass & 7) == 0 && wall_ticks() - t0 > limit) {
-            atomicExch(err, 1);
-            __hip_atomic_fetch_add(cnt, kXsBad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *s_stop = 1;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-        }
-      }
-    } else {
-      arrive(q, bad);
-      if (t < 64) poll(q, 0, (int)np);
-    }
-    __syncthreads();
-    return *s_stop == 0;
-  }
+  // one WAVE (all its lanes): wait until participants [lo, hi) have made arrival q (XcdFlags::wait)
+  __device__ bool poll(int q, int lo, int hi) const { return flags.wait(tag_of(q), lo, hi); }
 };
 
-// FG (fine-grained first barrier, BAR 1): the dW1 tile's epilogue, gated.  Each wave of the tile waits only for the
-// forward + head workgroups whose dZ1 column tiles its K range reads (samples [kbeg, kend) = column tiles
-// [kbeg / 32, ceil(kend / 32))), instead of the whole XCD; a wave that sees the launch stop marks the workgroup and
-// the update is then not applied (the K loop's reduction barrier orders that mark before the epilogue).
+// The dW1 tile's epilogue, gated.  Each wave of the tile waits only for the forward + head workgroups whose dZ1
+// column tiles its K range reads (samples [kbeg, kend) = column tiles [kbeg / 32, ceil(kend / 32))), not for the
+// whole XCD; a wave that sees the launch stop marks the workgroup and the update is then not applied (the K loop's
+// reduction barrier orders that mark before the epilogue).
 struct EpiW1Gate : EpiW1 {
-  XsBar<1>* bar;
+  const XsBar* bar;
   int q, tn;
-  const int* s_stop;
   __device__ void before_kloop(int kbeg, int kend) {
     if (kend > kbeg) bar->poll(q, kbeg / kXsCols, min(tn, (kend + kXsCols - 1) / kXsCols));
   }
   __device__ __forceinline__ void operator()(int qq, int row, int col, float v) {
-    if (!*s_stop) EpiW1::operator()(qq, row, col, v);
+    if (!*bar->flags.s_stop) EpiW1::operator()(qq, row, col, v);
   }
 };
 
@@ -221,19 +145,16 @@ struct EpiW1GateDiag : EpiW1Gate {
 };
 
 // The samples of a run_steps plan's steps: consecutive global batches of B from gstart0, wrapping to 0 when one
-// would pass N_end (MlpStep::run_steps), this rank's shard at +shard_off.  off() is the current step's first sample,
-// next() the following step's; advance() moves on by one step.
+// would pass N_end (MlpStep::run_steps), this rank's shard at +shard_off.  off() is the current step's first sample;
+// advance() moves on by one step.
 struct XsWalk {
   int64_t gs;
   const XStepPlan& p;
   __device__ explicit XsWalk(const XStepPlan& q) : gs(q.gstart0 + q.B > q.N_end ? 0 : q.gstart0), p(q) {}
   __device__ int64_t off() const { return gs + p.shard_off; }
-  __device__ int64_t next() const { return (gs + 2 * p.B > p.N_end ? 0 : gs + p.B) + p.shard_off; }
   __device__ void advance() { gs = gs + 2 * p.B > p.N_end ? 0 : gs + p.B; }
 };
 
-// FG: 0 two full XCD barriers per step; 1 the first fine-grained (EpiW1Gate); 2 both (the forward's waves wait for
-// their own dW1 tiles: fha_body's PsGate) -- no full barrier left, only flags.
 // DIAG: the diagnostics instantiation that honours the stamp buffers (XStepPlan::stamps, SplitStepArgs::stamps,
 // HeadArgs::stamps) and the hand-off test hook (SplitStepArgs::ag_test_skip); the production one has none of their
 // branches (dropping the stamps' took the walking step 9.86 -> 9.55 us, profiles/r6/xstep_ab_r6k_diag_templated.jsonl) (a runtime diagnostics branch in a production
@@ -245,19 +166,17 @@ struct XsWalk {
 // a step (mlp_split_wgrad vec 1 / 3) -- or, n % 4 == 0, 2 x 16-byte vectors with the tail past n zeroed in registers
 // (RM 4: the same MFMA operands as the two-launch step's element loads, vec 2; n = 100 walking step 9.25 -> 8.90 us,
 // profiles/r6/rm_form/), so the bits are its bits.
-// PIX (RM 0, barrier form 3): where the dW1 tile's pixel operand comes from (XStepPlan::pix).  0: the feature-major
+// PIX (RM 0): where the dW1 tile's pixel operand comes from (XStepPlan::pix).  0: the feature-major
 // copy XT, as the two-launch step reads it -- the same pixels the forward just pulled, at other addresses, so every
 // XCD fetches the batch a second time through the fabric.  1: the forward's fragment-ordered copy, which this XCD's
 // L2 holds, transposed through a wave-private LDS region (wsk_tile BLDS; the MFMA operands are the same registers,
 // so the bits are the same) -- the default: fabric read requests per step 97.5k -> 60.1k, L2 hit rate 76.6 -> 86.9 %,
 // the wave's first operands back 0.64 us sooner, walking step at n = 800 9.42-9.45 -> 9.30-9.34 us
 // (profiles/r7/README.md).
-template <int BAR, int FG, bool DIAG = false, int HK = 0, int RM = 0, int PIX = 0>
+template <bool DIAG, int HK, int RM, int PIX>
 __global__ __launch_bounds__(512) void xstep_kernel(SplitStepArgs a, HeadArgs h, XStepPlan p, int tm, int tn,
                                                     int t1n) {
-  static_assert(FG == 0 || BAR == 1, "the fine-grained barriers need the flag line");
-  static_assert(RM == 0 || (BAR == 1 && FG == 2), "the row-major form: barrier form 3");
-  static_assert(PIX == 0 || (RM == 0 && FG == 2), "the pixels through LDS: the fragment-ordered form, barrier form 3");
+  static_assert(PIX == 0 || RM == 0, "the pixels through LDS: the fragment-ordered form");
   constexpr int kSwz = RM == 0 ? 7 : 1;  // fha_body: fragment-ordered W1 (+ pixels and dZ1 in form 0)
   __shared__ __attribute__((aligned(16))) float red[8 * 1 * 2 * 4 * 64];  // both GEMM tiles' K reductions
   __shared__ __attribute__((aligned(16))) unsigned char pixl[PIX ? 8 * 4 * 1024 : 16];  // PIX: 4 KB per dW1 wave
@@ -271,10 +190,8 @@ __global__ __launch_bounds__(512) void xstep_kernel(SplitStepArgs a, HeadArgs h,
     if (x < 8) {
       slot = (int)__hip_atomic_fetch_add(xs_ticket(p.ctl, bank, (int)x), 1ull, __ATOMIC_RELAXED,
                                          __HIP_MEMORY_SCOPE_AGENT);
-      if (slot == 0) {  // the other bank, for the next launch (the previous launch that used it has ended)
+      if (slot == 0)  // the other bank, for the next launch (the previous launch that used it has ended)
         __hip_atomic_store(xs_ticket(p.ctl, bank ^ 1, (int)x), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(xs_counter(p.ctl, bank ^ 1, (int)x), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
     }
     s_x = x;
     s_slot = slot;
@@ -282,11 +199,9 @@ __global__ __launch_bounds__(512) void xstep_kernel(SplitStepArgs a, HeadArgs h,
   }
   __syncthreads();
   const int x = (int)s_x, slot = s_slot;
-  if (x >= tm || slot < 0 || slot > p.nw + p.npf) return;  // (uniform) XCDs past the last row tile, spare CUs
-  const uint32_t limit_us = (uint32_t)a.ag_wait_us;
-  // barrier participants: the workers + the role
-  XsBar<BAR> bar{xs_counter(p.ctl, bank, x), xs_flags(p.ctl, x), (unsigned long long)p.nw + 1, p.ep0, p.launch + 1u,
-                 slot, p.err, limit_us, &s_stop};
+  if (x >= tm || slot < 0 || slot > p.nw) return;  // (uniform) XCDs past the last row tile, spare CUs
+  // the flag line's participants: the workers + the role
+  XsBar bar{{xs_flags(p.ctl, x), p.launch + 1u, &s_stop, p.err, (uint32_t)a.ag_wait_us}, p.ep0, slot};
   const int n = a.n, ld = a.ld;
   const float reg = (float)a.reg, lr = (float)a.lr;
   unsigned long long* st = DIAG ? p.stamps : nullptr;  // diagnostics: [step][8][32][4]
@@ -294,39 +209,6 @@ __global__ __launch_bounds__(512) void xstep_kernel(SplitStepArgs a, HeadArgs h,
     if (st && t == 0 && s < p.stamp_steps)
       st[(((size_t)s * 8 + x) * kXsWgsPerXcd + slot) * 4 + i] = __builtin_amdgcn_s_memrealtime();
   };
-
-  if (slot > p.nw) {  // ---- prefetch (BAR 1): the pixels this XCD reads next, pulled into its L2 by idle CUs
-    if constexpr (BAR == 1 && FG == 0) {
-      // at the start of step s (the flag line says the previous step's second barrier is complete): this step's XT
-      // (the dW1 tiles read it after the first barrier) and the next step's fragment-ordered X (the next forward)
-      const int part = slot - p.nw - 1;
-      const unsigned* line = xs_flags(p.ctl, x);
-      XsWalk w(p);
-      for (int s = 0; s < p.count; ++s, w.advance()) {
-        if (s > 0 && t < 64) {
-          const unsigned tag = 2u * (p.ep0 + (unsigned)(s - 1)) + 1u, stop = p.launch + 1u;
-          const __amdgpu_buffer_rsrc_t rl = make_rsrc(line);
-          const uint64_t t0 = wall_ticks();
-          for (;;) {
-            const unsigned v = __builtin_amdgcn_raw_buffer_load_b32(rl, t < 32 ? t * 4 : kOOB, 0, kSc1);
-            if (__any(t == 31 && v == stop) || wall_ticks() - t0 > (uint64_t)limit_us * kTicksPerUs) {
-              if (t == 0) s_stop = 1;
-              break;
-            }
-            if (__all(t > p.nw || v - tag < 0x80000000u)) break;
-            __builtin_amdgcn_s_sleep(4);
-          }
-        }
-        __syncthreads();
-        if (s_stop) return;
-        l2_touch(p.XT0, w.off(), a.P + a.bias_col, a.ldxt, n, part, p.npf, reinterpret_cast<char*>(red));
-        if (s + 1 < p.count)
-          l2_touch(p.Xs0, w.next() / 16 * p.xs_tile, 1, 0, (int64_t)((n + 15) / 16) * p.xs_tile, part, p.npf,
-                   reinterpret_cast<char*>(red));
-      }
-    }
-    return;
-  }
 
   XsWalk w(p);
   for (int s = 0; s < p.count; ++s, w.advance()) {
@@ -346,69 +228,44 @@ __global__ __launch_bounds__(512) void xstep_kernel(SplitStepArgs a, HeadArgs h,
       hh.D = p.Dx + (size_t)x * 16 * ld;  // this XCD's copy of D (the role's db2 reads it)
       hh.b2 = s == 0 ? (const void*)a.b2 : (const void*)(p.b2x + x * 16);
       gran_t* slabs = p.gran + (size_t)(s & 1) * 32 * 8 * 16 * kXsCols;
-      if constexpr (FG == 2) {  // (the previous step's dW1 tiles and role, waited for per wave inside the GEMM)
-        PsGate gate;
-        gate.line = s > 0 ? xs_flags(p.ctl, x) : nullptr;
-        gate.tag = bar.tag_of(2 * s - 1);
-        gate.stop_tag = p.launch + 1u;
-        gate.ntiles = t1n;
-        gate.role = p.nw;
-        gate.s_stop = &s_stop;
-        gate.err = p.err;
-        gate.limit_us = limit_us;
-        bad = !fha_body<3, 3, true, kSwz, true, true, DIAG, HK>(f, hh, nullptr, slabs, p.err, tm, tn, slot * 8 + x, red,
-                                                             x, slot, p.ep0 + (unsigned)s, &gate);
-      } else {
-        bad = !fha_body<3, 3, true, 7, true, false, DIAG>(f, hh, nullptr, slabs, p.err, tm, tn, slot * 8 + x, red, x,
-                                                          slot, p.ep0 + (unsigned)s);
-      }
-    }  // (FG 2, a worker without a forward tile: the heads that overwrite what its dW1 tile read waited for it)
+      // (the previous step's dW1 tiles and role, waited for per wave inside the GEMM)
+      const PsGate gate{s > 0 ? &bar.flags : nullptr, bar.tag_of(2 * s - 1), t1n, p.nw};
+      bad = !fha_body<3, 3, true, kSwz, true, DIAG, HK>(f, hh, nullptr, slabs, p.err, tm, tn, slot * 8 + x, red, x, slot,
+                                                        p.ep0 + (unsigned)s, &gate, &s_stop);
+    }  // (a worker without a forward tile: the heads that overwrite what its dW1 tile read waited for it)
     stamp(s, 1);
-    if constexpr (FG > 0) {
-      bar.arrive(2 * s, bad);  // (the dW1 waves wait for their own column tiles, the role for all of them)
-    } else {
-      if (!bar.sync(2 * s, bad)) return;
-    }
+    bar.arrive(2 * s, bad);  // (the dW1 waves wait for their own column tiles, the role for all of them)
     stamp(s, 2);
     if (slot < p.nw) {
       if (slot < t1n) {  // ---- dW1 tile (x, slot) over the whole batch + reg + SGD (W1, W1s, b1)
         TileGeom g{a.H, a.P + a.bias_col, n, x * 16, slot * 32};
         const EpiW1 e1{a.W1, a.gW1, static_cast<bf16*>(a.W1p), (size_t)a.H * a.P, a.P, 1, 0, reg, lr, a.xscale, {},
                        a.b1, a.gb1, 0, nullptr};
-        if constexpr (FG > 0) {
-          auto dw1 = [&](auto& epi, unsigned long long* wst) {
-            epi.W1s = a.W1s;
-            if constexpr (RM == 0 && PIX != 0)
-              wsk_tile<bf16, 1, 2, 8, true, true, 3, 4, 3, uint8_t, float, true, false, kSc1, true>(
-                  a.dZ1, (ld + 63) / 64, p.Xs0 + off / 16 * p.xs_tile, (int)(p.xs_tile / 1024), g, epi, red, 0, wst,
-                  pixl, a.P);
-            else if constexpr (RM == 0)
-              wsk_tile<bf16, 1, 2, 8, true, true, 3, 4, 3, uint8_t, float, true, false, kSc1>(
-                  a.dZ1, (ld + 63) / 64, static_cast<const uint8_t*>(p.XT0) + off, a.ldxt, g, epi, red, 0, wst);
-            else
-              wsk_tile<bf16, 1, 2, 8, true, true, RM, 4, 3, uint8_t, float, false, false, kSc1>(
-                  a.dZ1, ld, static_cast<const uint8_t*>(p.XT0) + off, a.ldxt, g, epi, red, 0, wst);
-          };
-          if constexpr (DIAG) {  // (the last step's stamps stay: [256 workgroups][8 waves][4], then [256][8][2])
-            EpiW1GateDiag epi{{e1, &bar, 2 * s, tn, &s_stop},
-                              p.w1stamps ? p.w1stamps + 256 * 8 * 4 + ((size_t)blockIdx.x * 8 + (t >> 6)) * 2 : nullptr};
-            dw1(epi, p.w1stamps);
-          } else {
-            EpiW1Gate epi{e1, &bar, 2 * s, tn, &s_stop};
-            dw1(epi, nullptr);
-          }
-        } else {
-          EpiW1 epi = e1;
+        auto dw1 = [&](auto& epi, unsigned long long* wst) {
           epi.W1s = a.W1s;
-          wsk_tile<bf16, 1, 2, 8, true, true, 3, 4, 3, uint8_t, float, true, false, kSc1>(
-              a.dZ1, (ld + 63) / 64, static_cast<const uint8_t*>(p.XT0) + off, a.ldxt, g, epi, red, 0, nullptr);
+          if constexpr (RM == 0 && PIX != 0)
+            wsk_tile<bf16, 1, 2, 8, true, true, 3, 4, 3, uint8_t, float, true, false, kSc1, true>(
+                a.dZ1, (ld + 63) / 64, p.Xs0 + off / 16 * p.xs_tile, (int)(p.xs_tile / 1024), g, epi, red, 0, wst, pixl,
+                a.P);
+          else if constexpr (RM == 0)
+            wsk_tile<bf16, 1, 2, 8, true, true, 3, 4, 3, uint8_t, float, true, false, kSc1>(
+                a.dZ1, (ld + 63) / 64, static_cast<const uint8_t*>(p.XT0) + off, a.ldxt, g, epi, red, 0, wst);
+          else
+            wsk_tile<bf16, 1, 2, 8, true, true, RM, 4, 3, uint8_t, float, false, false, kSc1>(
+                a.dZ1, ld, static_cast<const uint8_t*>(p.XT0) + off, a.ldxt, g, epi, red, 0, wst);
+        };
+        if constexpr (DIAG) {  // (the last step's stamps stay: [256 workgroups][8 waves][4], then [256][8][2])
+          EpiW1GateDiag epi{{e1, &bar, 2 * s, tn},
+                            p.w1stamps ? p.w1stamps + 256 * 8 * 4 + ((size_t)blockIdx.x * 8 + (t >> 6)) * 2 : nullptr};
+          dw1(epi, p.w1stamps);
+        } else {
+          EpiW1Gate epi{e1, &bar, 2 * s, tn};
+          dw1(epi, nullptr);
         }
       }
-    } else {
-      if constexpr (FG > 0) {  // (the role reads every column tile's dW2 partials and D: it waits for all of them)
-        if (t < 64) bar.poll(2 * s, 0, tn);
-        __syncthreads();
-      }
+    } else {  // (the role reads every column tile's dW2 partials and D: it waits for all of them)
+      if (t < 64) bar.poll(2 * s, 0, tn);
+      __syncthreads();
     }
     if (slot == p.nw && !s_stop) {  // ---- the role: W2[:, x rows] from the dW2 partials and db2 into this XCD's b2
       // copy, side by side
@@ -478,12 +335,8 @@ __global__ __launch_bounds__(512) void xstep_kernel(SplitStepArgs a, HeadArgs h,
       }
     }
     stamp(s, 3);
-    if constexpr (FG == 2) {
-      bar.arrive(2 * s + 1, s_stop != 0);  // (the next forward's waves wait for the flags they need)
-      if (s_stop) return;
-    } else {
-      if (!bar.sync(2 * s + 1, s_stop != 0)) return;
-    }
+    bar.arrive(2 * s + 1, s_stop != 0);  // (the next forward's waves wait for the flags they need)
+    if (s_stop) return;
   }
 }
 
@@ -521,9 +374,8 @@ void mlp_xstep(const SplitStepArgs& a, const HeadArgs& h, const XStepPlan& p, hi
   if (p.count <= 0) return;
   CME_REQUIRE(mlp_xstep_ok(a, h), "xstep: the plan's step is not the XCD-local pipeline's shape");
   const int tm = xs_cdiv(a.H, 16), tn = xs_cdiv(a.n, kXsCols), t1n = xs_cdiv(a.P + a.bias_col, 32);
-  CME_REQUIRE(p.nw == mlp_xstep_workers(a) && p.nw + 1 + p.npf <= kXsWgsPerXcd && p.nw + 1 <= 31 && p.npf >= 0 &&
-                  (p.npf == 0 || p.bar == 1) && p.bar >= 0 && p.bar <= 3,
-              "xstep: the workers + the role (+ prefetch workgroups, flag-line barrier only) must fit one XCD's CUs");
+  CME_REQUIRE(p.nw == mlp_xstep_workers(a) && p.nw + 1 <= kXsWgsPerXcd && p.nw + 1 <= 31,
+              "xstep: the workers + the role must fit one XCD's CUs and its flag line");
   CME_REQUIRE(p.gran && p.ctl && p.Dx && p.b2x && p.err && p.X0 && p.XT0 && p.Xs0 && p.lab0 && p.xs_tile > 0,
               "xstep: scratch buffers missing");
   const bool grid16 = p.gstart0 % 16 == 0 && p.B % 16 == 0 && p.shard_off % 16 == 0;
@@ -535,28 +387,20 @@ void mlp_xstep(const SplitStepArgs& a, const HeadArgs& h, const XStepPlan& p, hi
               "aligned pixel columns)");
   CME_REQUIRE(a.ld >= a.n && a.ld % 16 == 0, "xstep: activation pitch");
   const bool diag = p.stamps || p.w1stamps || a.stamps || h.stamps || a.ag_test_skip >= 0;
-  CME_REQUIRE(!diag || p.bar == 3 || p.bar == 1,
-              "xstep: the stamps and the hand-off test hook exist in the diagnostics builds of barrier forms 1 and 3");
-  CME_REQUIRE(!rm || (p.bar == 3 && p.npf == 0 && !diag), "xstep: the row-major form exists in barrier form 3 only");
-  // (pix is honoured by the fragment-ordered form of barrier form 3 and its diagnostics build; every other form reads
-  // XT)
+  CME_REQUIRE(!rm || !diag, "xstep: the row-major form has no diagnostics build");
+  // (pix is honoured by the fragment-ordered form and its diagnostics build; the row-major form reads XT)
   CME_REQUIRE(p.pix == 0 || p.pix == 1, "xstep: the dW1 pixel operand's form is 0 (XT) or 1 (the forward's copy)");
-  if (rm == 1) xstep_kernel<1, 2, false, 7, 1><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
-  else if (rm == 4) xstep_kernel<1, 2, false, 7, 4><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
-  else if (rm == 3) xstep_kernel<1, 2, false, 7, 3><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
-  else if (diag && p.bar == 3 && p.pix == 1)
-    xstep_kernel<1, 2, true, 0, 0, 1><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
-  else if (diag && p.bar == 3) xstep_kernel<1, 2, true><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
-  else if (diag) xstep_kernel<1, 0, true><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
+  const dim3 grid_dim(8 * kXsWgsPerXcd), block(512);
+  if (rm == 1) xstep_kernel<false, 7, 1, 0><<<grid_dim, block, 0, s>>>(a, h, p, tm, tn, t1n);
+  else if (rm == 4) xstep_kernel<false, 7, 4, 0><<<grid_dim, block, 0, s>>>(a, h, p, tm, tn, t1n);
+  else if (rm == 3) xstep_kernel<false, 7, 3, 0><<<grid_dim, block, 0, s>>>(a, h, p, tm, tn, t1n);
+  else if (diag && p.pix == 1) xstep_kernel<true, 0, 0, 1><<<grid_dim, block, 0, s>>>(a, h, p, tm, tn, t1n);
+  else if (diag) xstep_kernel<true, 0, 0, 0><<<grid_dim, block, 0, s>>>(a, h, p, tm, tn, t1n);
   // (the production form keeps fha_body's three no-op runtime tests, HK = 7: measured 9.55-9.61 us against 9.81-9.86
   // without them and 9.62-9.94 with any one or two -- the compiler schedules the body differently; alternated four
   // and three times on two boxes, profiles/r6/hk/)
-  else if (p.bar == 3 && p.pix == 1)
-    xstep_kernel<1, 2, false, 7, 0, 1><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
-  else if (p.bar == 3) xstep_kernel<1, 2, false, 7><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
-  else if (p.bar == 2) xstep_kernel<1, 1><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
-  else if (p.bar == 1) xstep_kernel<1, 0><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
-  else xstep_kernel<0, 0><<<8 * kXsWgsPerXcd, 512, 0, s>>>(a, h, p, tm, tn, t1n);
+  else if (p.pix == 1) xstep_kernel<false, 7, 0, 1><<<grid_dim, block, 0, s>>>(a, h, p, tm, tn, t1n);
+  else xstep_kernel<false, 7, 0, 0><<<grid_dim, block, 0, s>>>(a, h, p, tm, tn, t1n);
   CME_LAUNCH_CHECK(s);
 }
 
