@@ -34,7 +34,7 @@ struct HeadArgs {
   int H, C, n;
   double scale;                   // D = (yhat - y) * scale, scale = 1/(n*R) (fpcode/neural_network.cpp:333)
   void* D;   int ldd;             // [C][ldd]
-  void* dZ1; int ldz;             // [H][ldz]
+  void* dZ1; int ldz;             // [H][ldz]; nullptr: not stored (only the bf16 shadow / the planes are wanted)
   void* dZ1_bf16;                 // optional bf16 shadow of dZ1 for the bf16 weight-gradient GEMM
   void* dZ1_planes = nullptr;     // optional exact bf16 planes of dZ1 ([npz][H][ldz]) for the split path
   int npz = 0;

@@ -248,7 +248,7 @@ __device__ __forceinline__ void head_block(const HeadArgs& a, const int vb, cons
     for (int c = 0; c < NC; ++c) da += w2(c, h) * z[c];
     const P dz = da * x * (P(1) - x);
     const size_t zi = (size_t)h * a.ldz + bcol;
-    dZ1[zi] = dz;
+    if (dZ1) dZ1[zi] = dz;  // nullptr: fp32 dZ1 not needed (shadow / planes only), as in the other heads
     if (dZlo) dZlo[zi] = __float2bfloat16((float)dz);
     if (dZp) {  // exact split into npz bf16 planes (mlp_split.h)
       float r = (float)dz;
@@ -428,7 +428,7 @@ __device__ __forceinline__ void head32(const HeadArgs& a, int ct, int t, Head32L
       const float x = xe[tt][j];
       const float dz = r[j] * x * (1.f - x);
       const size_t zi = (size_t)h * a.ldz + col;
-      dZ1[zi] = dz;
+      if (dZ1) dZ1[zi] = dz;  // nullptr: planes only
       if (dZlo) dZlo[zi] = __float2bfloat16(dz);
       if (dZp) {
         float rr = dz;
