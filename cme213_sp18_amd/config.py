@@ -48,6 +48,7 @@ class TrainConfig:
     overlap_chunks: int = 0     # RCCL path: dW1 all-reduce row chunks overlapped with the backward (0 = auto)
     parallel: str = "dp"        # dp (reference scheme) | tp (hidden-dimension tensor parallel, wide layers)
     num_classes: int = 10       # --classes: output classes (up to 64); labels must lie in [0, classes)
+    eval_every: int = 0         # --eval-every N: evaluate the resident dev split on the device every N epochs (dp)
     gpus: int = 0               # ranks (one per GPU); 0 = WORLD_SIZE of the launcher, else 1.  N > 1 without a
                                 # launcher: the CLI starts the N ranks itself (parallel/launcher.self_launch)
 
@@ -119,6 +120,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="output classes, 1..64 (default 10; e.g. 26 / 47 / 62 for the EMNIST splits): the layer sizes "
                          "become 784-H-N, synthetic data gets N classes, and labels read with --data must lie in "
                          "[0, N)")
+    ap.add_argument("--eval-every", type=int,
+                    help="keep the dev split resident on the device and evaluate it there after every N epochs "
+                         "(loss, accuracy, confusion matrix; `eval` events in --log-json); 0 = never (default)")
     ap.add_argument("--gpus", type=int,
                     help="number of ranks, one per GPU (the reference's mpirun -np N); started here when no "
                          "launcher started this process")

@@ -143,6 +143,7 @@ class MlpEngine:
         self.XT = None
         self.Xs = None  # the pixels in the forward's fragment order (load_dataset)
         self.labels = None
+        self._eval = None  # the resident validation set and its evaluation buffers (load_eval)
         self._normalize = False
         self.xscale = 1.0
         # keep a second, feature-major copy of the dataset ([P][N]) so the dW1 GEMM
@@ -626,3 +627,149 @@ class MlpEngine:
                     z2 = torch.sigmoid(z1) @ self.W2.t() + self.b2
                     out[s:e] = z2.argmax(dim=1).to(torch.int32)
         return out.cpu().numpy()
+
+    # -------------------------------------------------------------- evaluate
+    def load_eval(self, x, labels, eval_chunk: int | None = None, eval_slots: int = 1):
+        """Upload a validation set once ([N][P]) and keep it resident next to the training set, with everything an
+        evaluation needs: the a1 scratch for ``eval_chunk`` columns (default as predict: max(ld, 4096)), the loss
+        partials and ``eval_slots`` stats slots (csrc/mlp/eval.h: n, correct, loss_sum, C x C confusion counts, rows
+        = labels).  Split paths keep raw uint8 pixels, range-checked once here; the others the GEMM dtype with the
+        training set's ``normalize``.  No evaluation allocates anything afterwards."""
+        xt = torch.as_tensor(np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x)
+        if xt.ndim != 2 or xt.shape[1] != self.P:
+            raise ValueError(f"expected [N][{self.P}] samples, got {tuple(xt.shape)}")
+        lab = torch.as_tensor(np.asarray(labels, dtype=np.int64)).reshape(-1)
+        n = int(xt.shape[0])
+        if int(lab.numel()) != n:
+            raise ValueError("one label per sample expected")
+        if n and (int(lab.min()) < 0 or int(lab.max()) >= self.C):
+            raise ValueError(f"labels must be in [0, {self.C})")
+        if int(eval_slots) < 1:
+            raise ValueError("eval_slots must be >= 1")
+        xd = xt.to(self.device)
+        if self.np:
+            raw = xd.to(torch.float32)
+            if not bool(((raw == raw.round()) & (raw >= 0) & (raw <= 255)).all().item()):
+                raise ValueError("split-path evaluation needs raw 0..255 pixel inputs")
+            X = raw.to(torch.uint8).contiguous()
+        else:
+            xd = xd.to(torch.float64 if self.dtype == "f64" else torch.float32)
+            if self._normalize:
+                xd = xd / 255.0
+            X = xd.to(self.gdt).contiguous()
+        chunk = int(eval_chunk or max(self.ld, 4096))
+        if chunk < 1:
+            raise ValueError("eval_chunk must be >= 1")
+        cols = _round_up(max(1, min(chunk, n)), 16)
+        words = 3 + self.C * self.C
+        self._eval = dict(
+            X=X, labels=lab.to(torch.int32).to(self.device).contiguous(), n=n, chunk=chunk, path=self.path,
+            a1=torch.zeros(self.H, cols, dtype=self.pdt, device=self.device),
+            partials=torch.zeros(256, dtype=torch.float64, device=self.device),  # (eval.h kEvalMaxWgs)
+            stats=torch.zeros(int(eval_slots), words, dtype=torch.int64, device=self.device))
+
+    @property
+    def eval_samples(self) -> int:
+        return self._eval["n"] if self._eval is not None else 0
+
+    @property
+    def eval_slots(self) -> int:
+        return int(self._eval["stats"].shape[0]) if self._eval is not None else 0
+
+    def reserve_eval_slots(self, slots: int) -> None:
+        """At least ``slots`` stats slots (allocates; call before the evaluations are enqueued, never between an
+        enqueue and its read, and not while a captured evaluation is to be replayed)."""
+        ev = self._eval
+        if ev is None:
+            raise RuntimeError("load_eval() first")
+        if int(slots) > ev["stats"].shape[0]:
+            ev["stats"] = torch.zeros(int(slots), ev["stats"].shape[1], dtype=torch.int64, device=self.device)
+
+    def _eval_set(self, slot: int):
+        ev = self._eval
+        if ev is None:
+            raise RuntimeError("load_eval() first")
+        if ev["path"] != self.path:
+            raise RuntimeError("the compute path changed after load_eval(): load the validation set again")
+        if not 0 <= int(slot) < ev["stats"].shape[0]:
+            raise IndexError(f"evaluation slot {slot} outside [0, {ev['stats'].shape[0]})")
+        return ev
+
+    def enqueue_eval(self, slot: int, first: int = 0, count: int | None = None) -> None:
+        """Enqueue the evaluation of validation samples [first, first + count) into stats slot ``slot`` on the
+        current stream, chunk by chunk: forward GEMM into the a1 scratch, then the evaluation head.  The first chunk
+        clears the slot.  No host read, no sync, no allocation: legal under stream capture."""
+        ev = self._eval_set(slot)
+        count = ev["n"] - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > ev["n"]:
+            raise IndexError("evaluation range outside the resident validation set")
+        if self.backend != "hip":
+            self._torch_eval(ev, int(slot), int(first), count)
+            return
+        m = hip()
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        a1, lda = ev["a1"].data_ptr(), int(ev["a1"].shape[1])
+        stats = ev["stats"].data_ptr() + int(slot) * ev["stats"].shape[1] * 8
+        part = ev["partials"].data_ptr()
+        x0, l0, xrow = ev["X"].data_ptr(), ev["labels"].data_ptr(), self.P * ev["X"].element_size()
+        step = min(ev["chunk"], lda)
+        dt = DTYPE_CODES[self.dtype]
+        if count == 0:  # an empty shard still clears its slot
+            m.mlp_eval_head(0 if self.dtype == "bf16" else dt, 0, lda, self.W2.data_ptr(), self.b2.data_ptr(), 0,
+                            self.H, self.C, 0, stats, part, 1, st)
+            return
+        for s in range(first, first + count, step):
+            nb = min(step, first + count - s)
+            zero = int(s == first)
+            if self.np:
+                self._hip_step().evaluate(x0 + s * xrow, l0 + 4 * s, nb, a1, lda, stats, part, st, zero)
+            else:
+                m.mlp_forward1(dt, self.W1g.data_ptr(), self.b1.data_ptr(), x0 + s * xrow, self.P, self.H, nb, a1,
+                               lda, 1, st)
+                m.mlp_eval_head(0 if self.dtype == "bf16" else dt, a1, lda, self.W2.data_ptr(), self.b2.data_ptr(),
+                                l0 + 4 * s, self.H, self.C, nb, stats, part, zero, st)
+
+    def _torch_eval(self, ev, slot: int, first: int, count: int) -> None:
+        """The evaluation head's math in torch ops (param dtype z2 and nll, fp64 loss accumulation)."""
+        C = self.C
+        with torch.no_grad():
+            row = ev["stats"][slot]
+            row.zero_()
+            loss = row[2:3].view(torch.float64)
+            cls = torch.arange(C, device=self.device)
+            step = ev["chunk"]
+            for s in range(first, first + count, step):
+                e = min(first + count, s + step)
+                W1e = self.W1p.to(self.pdt).sum(0) if self.np else self.W1g.to(self.pdt)
+                z1 = (ev["X"][s:e].to(self.pdt) * self.xscale) @ W1e.t() + self.b1
+                z2 = torch.sigmoid(z1) @ self.W2.t() + self.b2
+                lab = ev["labels"][s:e].long()
+                mx = z2.max(dim=1, keepdim=True).values
+                pred = torch.where(z2 == mx, cls, C).min(dim=1).values  # the first maximum
+                nll = torch.log(torch.exp(z2 - mx).sum(1)) - (z2.gather(1, lab[:, None])[:, 0] - mx[:, 0])
+                row[0] += e - s
+                row[1] += (pred == lab).sum()
+                loss += nll.double().sum()
+                row[3:] += torch.bincount(lab * C + pred, minlength=C * C)
+
+    def eval_words(self, slots: int | None = None, first: int = 0) -> torch.Tensor:
+        """Host copy of stats slots [first, first + slots) as raw 8-byte words [slots][3 + C * C] (word 2 is the fp64
+        loss_sum's bits): the one sync and copy of an evaluation."""
+        ev = self._eval_set(first)
+        k = ev["stats"].shape[0] - first if slots is None else int(slots)
+        self._eval_set(first + max(k, 1) - 1)
+        return ev["stats"][first:first + k].cpu()
+
+    def unpack_eval(self, words: torch.Tensor) -> dict:
+        """One slot's words -> dict(n, correct, loss_sum, confusion [C][C] int64, rows = labels)."""
+        C = self.C
+        return dict(n=int(words[0]), correct=int(words[1]), loss_sum=float(words[2:3].view(torch.float64)[0]),
+                    confusion=words[3:].view(C, C).numpy().copy())
+
+    def read_eval(self, slot: int = 0) -> dict:
+        ev = self._eval_set(slot)
+        return self.unpack_eval(ev["stats"][int(slot)].cpu())
+
+    def evaluate(self, slot: int = 0, first: int = 0, count: int | None = None) -> dict:
+        self.enqueue_eval(slot, first, count)
+        return self.read_eval(slot)

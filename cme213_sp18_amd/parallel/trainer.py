@@ -222,6 +222,8 @@ class TrainStats:
     steps: int = 0
     images: int = 0
     losses: list = field(default_factory=list)
+    # train(eval_every=k): one {epoch, iter, n, loss, accuracy, confusion} per evaluated epoch
+    evals: list = field(default_factory=list)
 
     @property
     def images_per_sec(self) -> float:
@@ -515,6 +517,50 @@ class DataParallelTrainer:
             self.fused_allreduce = self._check_fused()
             self.allreduce_impl = ("xgmi-push" if self.fused_form == "push" else "xgmi-fused") \
                 if self.fused_allreduce else "xgmi"
+
+    def load_eval(self, x, y, eval_chunk: int | None = None) -> None:
+        """Keep a validation set resident for evaluate() / train(eval_every=k).  Rank r holds and evaluates the
+        contiguous shard [r n // R, (r + 1) n // R): every sample is covered once (nothing is dropped, unlike the
+        training shard)."""
+        n = int(np.asarray(y).shape[0])
+        lo, hi = self.rank * n // self.R, (self.rank + 1) * n // self.R
+        self.engine.load_eval(x[lo:hi], np.asarray(y)[lo:hi], eval_chunk=eval_chunk)
+
+    def _read_evals(self, slots: int, first: int = 0) -> list[dict]:
+        """Stats slots [first, first + slots): one sync and copy, then ONE all-reduce of the packed host tensor
+        (counts are exact in fp64) -- every rank returns the same records.  Collective."""
+        e = self.engine
+        words = e.eval_words(slots, first)
+        if self.R > 1:
+            packed = words.to(torch.float64)
+            packed[:, 2] = words[:, 2].contiguous().view(torch.float64)
+            from .comm import TorchDistComm
+
+            if isinstance(self.comm, TorchDistComm) and self.comm.backend == "nccl":
+                dev = packed.to(e.device)
+                self.comm.allreduce_(dev)
+                packed = dev.cpu()
+            else:
+                self.comm.allreduce_(packed)
+            loss_bits = packed[:, 2].clone().view(torch.int64)
+            packed[:, 2] = 0.0
+            words = packed.round().to(torch.int64)
+            words[:, 2] = loss_bits
+        out = []
+        for w in words:
+            r = e.unpack_eval(w)
+            n = r["n"]
+            out.append({"n": n, "loss": r["loss_sum"] / n if n else float("nan"),
+                        "accuracy": r["correct"] / n if n else float("nan"), "confusion": r["confusion"]})
+        return out
+
+    def evaluate(self) -> dict:
+        """Evaluate the resident validation set with the current parameters: dict(n, loss, accuracy, confusion) --
+        loss is the mean nll without the regulariser, confusion [C][C] with rows = labels.  Collective."""
+        if self.engine.eval_slots == 0:
+            raise RuntimeError("load_eval() first")
+        self.engine.enqueue_eval(0)
+        return self._read_evals(1)[0]
 
     def _check_fused(self) -> bool:
         """One step from the same state through both all-reduce paths (separate xGMI kernel, and
@@ -833,7 +879,7 @@ class DataParallelTrainer:
     # ---------------------------------------------------------------- train
     def train(self, epochs: int, lr: float, reg: float, print_every: int = 0, debug: bool = False,
               outdir: str = "Outputs", log=print, on_event=None, fault: tuple[int, int] | None = None,
-              diff_file=None) -> TrainStats:
+              diff_file=None, eval_every: int = 0) -> TrainStats:
         """Full training loop (neural_network.cpp:446-555).  Eager steps where the
         host must look at a step (loss printing / debug diffs), graphs elsewhere.
 
@@ -845,6 +891,13 @@ class DataParallelTrainer:
         diff_file: an open text file for the -d CPU-vs-GPU diff rows (the caller owns it across
         several train() segments); None: this call opens Outputs/CpuGpuDiff.txt itself -- truncated
         on a fresh run (iter 0), appended to when training resumes mid-run.
+
+        eval_every=k > 0 (after load_eval): after epochs k, 2k, ... the resident validation set is evaluated on the
+        device, enqueued behind that epoch's plan into its own stats slot (epochs // k slots, reserved up front); the
+        slots are read once after the last epoch into ``TrainStats.evals`` -- {epoch, iter, n, loss, accuracy,
+        confusion}, epoch counted from 0 as in the other events.  A slot is read earlier only when the host looks at
+        the epoch anyway (on_event, print_every, debug -- the same on every rank: the read is collective): then an
+        {"event": "eval", ...} record without the matrix goes to on_event and rank 0 logs one line.
 
         With the xGMI all-reduce, every epoch ends with a collective check of the peer-wait error flag
         (assert_comm_ok): a timed-out wait raises CommFailure on every rank before another epoch runs."""
@@ -860,6 +913,32 @@ class DataParallelTrainer:
         xgmi_live = self.xgmi is not None or self._xgmi_fused is not None
         ag_live = self._allgather_live()  # all-gather forward + head launches: their timeout flag, per epoch
         host_needed = print_every > 0 or debug or self.profiler is not None
+        eval_every = max(0, int(eval_every))
+        n_ev = epochs // eval_every if eval_every else 0
+        if eval_every:
+            if self.engine.eval_slots == 0:
+                raise RuntimeError("train(eval_every=...): load_eval() first")
+            self.engine.reserve_eval_slots(max(1, n_ev))
+        host_looks = on_event is not None or print_every > 0 or debug
+        ev_meta: dict = {}  # slot -> (epoch, iter) of the evaluations enqueued
+        ev_read: dict = {}  # slot -> record, for the slots read before the end
+
+        def eval_slot(epoch: int) -> int:
+            return (epoch + 1) // eval_every - 1 if eval_every and (epoch + 1) % eval_every == 0 else -1
+
+        def eval_enqueued(slot: int, epoch: int) -> None:
+            ev_meta[slot] = (epoch, self.iter)
+            ev_read.pop(slot, None)  # (a re-run epoch overwrote the slot)
+            if not host_looks:
+                return
+            r = self._read_evals(1, slot)[0]
+            ev_read[slot] = r
+            if self.rank == 0:
+                log(f"Validation after epoch {epoch}/{epochs}: loss = {r['loss']:.10g}, "
+                    f"accuracy = {r['accuracy']:.6g} (n = {r['n']})")
+            if on_event is not None:
+                on_event({"event": "eval", "epoch": epoch, "iter": self.iter, "n": r["n"], "loss": r["loss"],
+                          "accuracy": r["accuracy"]})
         dev = self.engine.device
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
@@ -874,11 +953,16 @@ class DataParallelTrainer:
                 maybe_fault(self.iter, len(plan.steps))
                 with self.roctx.range(f"epoch {epoch}"):
                     self.run_plan(plan, lr, reg)
+                slot = eval_slot(epoch)
+                if slot >= 0:  # behind the epoch's plan, ahead of the epoch's sync (if any)
+                    self.engine.enqueue_eval(slot)
                 if xgmi_live or ag_live:
                     self.assert_comm_ok()  # syncs; every rank raises together
                 self.iter += len(plan.steps)
                 stats.steps += len(plan.steps)
                 stats.images += sum((ln // self.R) * self.R for _, ln in plan.steps)
+                if slot >= 0:
+                    eval_enqueued(slot, epoch)
                 if on_event is not None:
                     if dev.type == "cuda":
                         torch.cuda.synchronize(dev)
@@ -905,8 +989,13 @@ class DataParallelTrainer:
                 self.iter += 1
                 stats.steps += 1
                 stats.images += (ln // self.R) * self.R
+            slot = eval_slot(epoch)
+            if slot >= 0:
+                self.engine.enqueue_eval(slot)
             if xgmi_live or ag_live:
                 self.assert_comm_ok()
+            if slot >= 0:
+                eval_enqueued(slot, epoch)
 
         try:
             for epoch in range(epochs):
@@ -930,6 +1019,12 @@ class DataParallelTrainer:
                 # the xGMI hand-off's ordering rests on write-through stores (csrc/comm/xgmi_allreduce.hip):
                 # a stale peer read would leave the replicas different -- checked bitwise once per train()
                 raise CommFailure(f"rank {self.rank}: replicas differ after xGMI data-parallel training")
+            if n_ev:  # the slots not read yet: one copy, one all-reduce
+                if len(ev_read) < n_ev:
+                    recs = self._read_evals(n_ev)
+                    for s_ in range(n_ev):
+                        ev_read.setdefault(s_, recs[s_])
+                stats.evals = [{"epoch": ev_meta[s_][0], "iter": ev_meta[s_][1], **ev_read[s_]} for s_ in range(n_ev)]
             self.comm.barrier()
         finally:
             if own_file:

@@ -135,6 +135,12 @@ def run(cfg: TrainConfig) -> dict:
                                      normalize=cfg.normalize, path=cfg.path, allreduce=cfg.allreduce,
                                      overlap_chunks=cfg.overlap_chunks)
         tr.load(ds.x_train, ds.y_train)
+        eval_every = cfg.eval_every if cfg.parallel != "tp" else 0
+        if cfg.eval_every > 0 and not eval_every:
+            log0(rank, "note: --eval-every is data-parallel only; ignored with --parallel tp")
+        if eval_every > 0:
+            tr.load_eval(ds.x_dev, ds.y_dev)
+        train_kw = {"eval_every": eval_every} if eval_every > 0 else {}
         # a resumed run continues the iteration counter (loss lines, -d diff rows and the print_flag
         # schedule pick up where the checkpoint left off; CpuGpuDiff.txt is appended to, not truncated)
         tr.iter = int(meta.get("iter", 0))
@@ -148,13 +154,14 @@ def run(cfg: TrainConfig) -> dict:
         while done < cfg.num_epochs or st is None:  # train in checkpoint segments
             k = min(seg, cfg.num_epochs - done)
             s1 = tr.train(k, cfg.learning_rate, cfg.reg, print_every=cfg.print_every, debug=cfg.debug,
-                          outdir=cfg.outdir, log=lambda m: log0(rank, m), on_event=jlog, fault=fault)
+                          outdir=cfg.outdir, log=lambda m: log0(rank, m), on_event=jlog, fault=fault, **train_kw)
             st = s1 if st is None else st
             if st is not s1:
                 st.seconds += s1.seconds
                 st.steps += s1.steps
                 st.images += s1.images
                 st.losses += s1.losses
+                st.evals += s1.evals
             done += k
             if cfg.ckpt_dir and done < cfg.num_epochs:
                 if rank == 0:

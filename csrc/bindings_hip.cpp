@@ -110,6 +110,20 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       py::arg("D") = 0, py::arg("ldd") = 0, py::arg("dZ1") = 0, py::arg("ldz") = 0, py::arg("dZ1_bf16") = 0,
       py::arg("loss") = 0, py::arg("pred") = 0, py::arg("probs") = 0, py::arg("ldp") = 0,
       py::arg("shift") = 1, py::arg("stream") = 0, py::arg("dZ1_planes") = 0, py::arg("npz") = 0);
+  m.def(
+      "mlp_eval_head",
+      [](int dt, uintptr_t a1, int lda, uintptr_t W2, uintptr_t b2, uintptr_t labels, int H, int C, int n,
+         uintptr_t stats, uintptr_t partials, int zero, uintptr_t s) {
+        cme::EvalArgs e{};
+        e.a1 = P<void>(a1); e.lda = lda; e.W2 = P<void>(W2); e.b2 = P<void>(b2); e.labels = P<int>(labels);
+        e.H = H; e.C = C; e.n = n; e.stats = P<unsigned long long>(stats); e.partials = P<double>(partials);
+        e.zero = zero;
+        cme::mlp_eval_head(to_dt(dt), e, S(s));
+      },
+      py::arg("dt"), py::arg("a1"), py::arg("lda"), py::arg("W2"), py::arg("b2"), py::arg("labels"), py::arg("H"),
+      py::arg("C"), py::arg("n"), py::arg("stats"), py::arg("partials"), py::arg("zero") = 1, py::arg("stream") = 0);
+  m.def("mlp_eval_num_partials", &cme::mlp_eval_num_partials, py::arg("n"));
+  m.def("mlp_eval_slot_words", &cme::mlp_eval_slot_words, py::arg("C"));
   m.def("mlp_head_num_blocks", &cme::mlp_head_num_blocks);
   m.def("head_big_scratch_floats", &cme::head_big_scratch_floats);
 
@@ -235,6 +249,8 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
            py::arg("lr"), py::arg("sgd"), py::arg("parts"), py::arg("row0"), py::arg("rows"), py::arg("stream"))
       .def("predict", &MlpStep::predict, py::arg("x"), py::arg("n"), py::arg("a1buf"), py::arg("lda"),
            py::arg("pred"), py::arg("stream"))
+      .def("evaluate", &MlpStep::evaluate, py::arg("x"), py::arg("labels"), py::arg("n"), py::arg("a1buf"),
+           py::arg("lda"), py::arg("stats"), py::arg("partials"), py::arg("stream"), py::arg("zero") = 0)
       .def("run", &MlpStep::run, py::arg("off"), py::arg("n"), py::arg("scale"), py::arg("reg"), py::arg("lr"),
            py::arg("sgd"), py::arg("with_loss"), py::arg("stream"), py::arg("parts") = 3, py::arg("pf_next") = -1);
 

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <string>
 
+#include "eval.h"
 #include "mlp_kernels.h"
 #include "mlp_split.h"
 
@@ -231,6 +232,13 @@ struct MlpStep {
   // tiled forward (wave-split-K: the wide engines' bf16 copies are of the training set, not of x)
   // into a1buf, then the column head in predict mode
   void predict(uintptr_t x, int n, uintptr_t a1buf, int lda, uintptr_t pred, uintptr_t stream);
+  // split path forward + evaluation head (eval.h) for n samples at x (uint8 [n][P]) with labels (int32 [n]): the same
+  // forward as predict into a1buf, then loss / hits / confusion counts into the slot `stats` (partials: the head's
+  // loss scratch).  zero = 1 on an evaluation's first chunk.  Enqueues only (legal under stream capture; there the
+  // first chunk re-splits the W1 planes whenever a step's in-place update may leave them stale -- the replay cannot
+  // decide -- and the later chunks of the captured evaluation rely on it)
+  void evaluate(uintptr_t x, uintptr_t labels_, int n, uintptr_t a1buf, int lda, uintptr_t stats, uintptr_t partials,
+                uintptr_t stream, int zero = 0);
   bool w1_planes_read() const {  // a forward kernel of this step reads the W1 planes (else: not refreshed)
     return split != 0 && mlp_split_w1_planes_read(split_args(0, ld, 1.0, 0.0, 0.0, 1, 0));
   }

@@ -435,4 +435,36 @@ void MlpStep::predict(uintptr_t x, int n, uintptr_t a1buf, int lda, uintptr_t pr
   mlp_head(DType::F32, h, S(stream));
 }
 
+void MlpStep::evaluate(uintptr_t x, uintptr_t labels_, int n, uintptr_t a1buf, int lda, uintptr_t stats,
+                       uintptr_t partials, uintptr_t stream, int zero) {
+  CME_REQUIRE(split && n >= 0 && n <= lda, "MlpStep.evaluate: split path, 0 <= n <= lda");
+  EvalArgs e{};
+  e.a1 = reinterpret_cast<const void*>(a1buf); e.lda = lda; e.W2 = P_<float>(W2); e.b2 = P_<float>(b2);
+  e.labels = P_<int>(labels_); e.H = H; e.C = C; e.n = n;
+  e.stats = P_<unsigned long long>(stats); e.partials = P_<double>(partials); e.zero = zero;
+  if (n > 0) {
+    // a captured evaluation is replayed after steps the host does not see: where their in-place update leaves the
+    // W1 planes stale and this forward reads them, the re-split is part of the capture whatever planes_stale says
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_CHECK(hipStreamIsCapturing(S(stream), &cap));
+    if (cap == hipStreamCaptureStatusNone) {
+      refresh_planes(stream);
+    } else if (zero) {  // (the first chunk's re-split covers the later chunks of the captured evaluation)
+      const bool stale = planes_stale;
+      if (stale || (W1p && lazy_planes_apply())) {
+        planes_stale = true;
+        refresh_planes(stream);
+      }
+      planes_stale = stale;  // (a captured re-split has not run)
+    }
+    SplitStepArgs a = split_args(0, n, 1.0, 0.0, 0.0, 0, 0);
+    a.X = reinterpret_cast<const void*>(x);
+    a.Xw = nullptr;
+    a.a1 = reinterpret_cast<float*>(a1buf);
+    a.ld = lda;
+    mlp_split_fwd1(a, S(stream));
+  }
+  mlp_eval_head(DType::F32, e, S(stream));
+}
+
 }  // namespace cme
