@@ -49,6 +49,7 @@ class TrainConfig:
     parallel: str = "dp"        # dp (reference scheme) | tp (hidden-dimension tensor parallel, wide layers)
     num_classes: int = 10       # --classes: output classes (up to 64); labels must lie in [0, classes)
     eval_every: int = 0         # --eval-every N: evaluate the resident dev split on the device every N epochs (dp)
+    shuffle_seed: int | None = None  # --shuffle-seed S: reshuffle the resident training set on the device every epoch
     gpus: int = 0               # ranks (one per GPU); 0 = WORLD_SIZE of the launcher, else 1.  N > 1 without a
                                 # launcher: the CLI starts the N ranks itself (parallel/launcher.self_launch)
 
@@ -123,6 +124,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--eval-every", type=int,
                     help="keep the dev split resident on the device and evaluate it there after every N epochs "
                          "(loss, accuracy, confusion matrix; `eval` events in --log-json); 0 = never (default)")
+    ap.add_argument("--shuffle-seed", type=int,
+                    help="reshuffle the resident training set on the device before every epoch (sequential and "
+                         "parallel run alike; the order depends on the seed and the iteration counter only, so "
+                         "--resume continues the sequence); default: the loaded order every epoch")
     ap.add_argument("--gpus", type=int,
                     help="number of ranks, one per GPU (the reference's mpirun -np N); started here when no "
                          "launcher started this process")

@@ -107,10 +107,16 @@ def numgrad(nn: NeuralNetwork, X, labels, reg: float, shift: bool = True) -> Gra
 
 def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, epochs: int = 15,
           batch_size: int = 800, grad_check: bool = False, print_every: int = -1, debug: bool = False,
-          outdir: str = "Outputs", shift: bool = True, ckpt_precision: int = 12, iter0: int = 0) -> list[float]:
+          outdir: str = "Outputs", shift: bool = True, ckpt_precision: int = 12, iter0: int = 0,
+          shuffle_seed: int | None = None) -> list[float]:
     """Sequential fp64 minibatch SGD on the CPU -- the oracle (neural_network.cpp:219-279).
 
     ``iter0``: the iteration counter at the start -- a resumed run continues the loss / snapshot numbering.
+
+    ``shuffle_seed``: the parallel trainers' per-epoch shuffle (DataParallelTrainer(shuffle_seed=...)): one native
+    epoch at a time on ``X[perm_e]``, perm_e = epoch_permutation(N, seed, iteration counter at the epoch start) -- the
+    one implementation in csrc/mlp/shuffle.h -- with the counter carried, so the oracle stays comparable with a
+    shuffled parallel run.
 
     ``grad_check`` runs a numerical gradient check on the first batch (the
     reference's threshold of 1000 made it a no-op; we assert a real bound).
@@ -126,5 +132,17 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
         ng = numgrad(nn, X[:n], labels[:n], reg, shift)
         if not gradcheck(ng, g):
             raise AssertionError("gradient check failed")
-    return list(cpu().train(*nn.params, X, labels, float(learning_rate), float(reg), int(epochs), int(batch_size),
-                            int(print_every), bool(debug), outdir, shift, int(ckpt_precision), int(iter0)))
+    if shuffle_seed is None:
+        return list(cpu().train(*nn.params, X, labels, float(learning_rate), float(reg), int(epochs),
+                                int(batch_size), int(print_every), bool(debug), outdir, shift, int(ckpt_precision),
+                                int(iter0)))
+    losses: list[float] = []
+    n = X.shape[0]
+    it = int(iter0)
+    for _ in range(int(epochs)):
+        perm = cpu().epoch_permutation(n, int(shuffle_seed), it)
+        losses += cpu().train(*nn.params, np.ascontiguousarray(X[perm]), np.ascontiguousarray(labels[perm]),
+                              float(learning_rate), float(reg), 1, int(batch_size), int(print_every), bool(debug),
+                              outdir, shift, int(ckpt_precision), it)
+        it += (n + int(batch_size) - 1) // int(batch_size)
+    return losses

@@ -24,7 +24,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .._native import DTYPE_CODES, hip
+from .._native import DTYPE_CODES, cpu, hip
 
 _ALIGN = 64  # elements; keeps every arena segment 256-byte aligned for f32
 
@@ -143,6 +143,9 @@ class MlpEngine:
         self.XT = None
         self.Xs = None  # the pixels in the forward's fragment order (load_dataset)
         self.labels = None
+        # the pristine rows as loaded (load_dataset(keep_source=True)): what enqueue_shuffle gathers from
+        self.X0 = self.labels0 = self._perm = None
+        self.shuffle_launches = 0  # shuffle kernel launches enqueued (0: the kernel was never loaded)
         self._eval = None  # the resident validation set and its evaluation buffers (load_eval)
         self._normalize = False
         self.xscale = 1.0
@@ -233,8 +236,11 @@ class MlpEngine:
             self.ag_gran = torch.zeros(((H + 63) // 64 * 16 + 16) * ld, dtype=torch.int64, device=dev)
         self._step = None
 
-    def load_dataset(self, x, labels, normalize: bool = False):
+    def load_dataset(self, x, labels, normalize: bool = False, keep_source: bool = False):
         """Upload the training set once ([N][P] uint8 or float) and keep it resident.
+
+        ``keep_source``: also keep a pristine copy of the rows and labels as loaded (``X0`` / ``labels0``, in the
+        resident dtype) and an int32 order buffer, so that enqueue_shuffle can rewrite the layouts in another order.
 
         Split paths keep the RAW uint8 pixels (1 byte/element; widened to bf16
         exactly inside the GEMM kernels, normalisation folded into the epilogues
@@ -283,8 +289,71 @@ class MlpEngine:
             self.XTw = self.XT.to(torch.bfloat16).contiguous()
         self.labels = torch.as_tensor(np.asarray(labels, dtype=np.int32)).to(self.device).contiguous()
         self.num_samples = int(self.X.shape[0])
+        self.X0 = self.labels0 = self._perm = None
+        if keep_source:
+            # the loaded tensors become the (never written) source and the step reads fresh copies: on the CPU the
+            # loaded ones may share memory with the caller's arrays, which a shuffle must not rewrite
+            self.X0, self.labels0 = self.X, self.labels
+            self.X, self.labels = self.X0.clone(), self.labels0.clone()
+            if self.XT is not None and self.XT.data_ptr() == self.X0.data_ptr():  # (N == 1: the transpose is a view)
+                self.XT = self.XT.clone()
+            self._perm = torch.arange(self.num_samples, dtype=torch.int32, device=self.device)
         self._step = None
         self.refresh_shadow()
+
+    # ------------------------------------------------------- per-epoch shuffle
+    def enqueue_shuffle(self, seed: int, key: int) -> None:
+        """Rewrite every resident layout (X, labels, XT, Xs, Xw, XTw) in place so that sample i is SOURCE sample
+        perm[i], perm = epoch_permutation(N, seed, key) (csrc/mlp/shuffle.h; seed and key are unsigned 32-bit, packed
+        as (seed << 32) ^ key).  Always gathers from the pristine copy, never from the previous order, so the order
+        depends on (seed, key) alone.  On the current stream; no sync, no read-back, no allocation on the hip backend:
+        the buffers keep their addresses, so a bound MlpStep and every captured graph stay valid."""
+        self._shuffle(int(seed), int(key), False)
+
+    def unshuffle(self) -> None:
+        """The order of load_dataset() again."""
+        self._shuffle(0, 0, True)
+
+    def permutation(self) -> torch.Tensor:
+        """The current order as a device int32 tensor: resident sample i is loaded sample permutation()[i] (the
+        identity before any shuffle)."""
+        if self._perm is not None:
+            return self._perm
+        if self.X is None:
+            raise RuntimeError("load_dataset() first")
+        return torch.arange(self.num_samples, dtype=torch.int32, device=self.device)
+
+    def _shuffle(self, seed: int, key: int, identity: bool) -> None:
+        if self.X is None:
+            raise RuntimeError("load_dataset() first")
+        if self.X0 is None:
+            raise RuntimeError("no pristine copy of the training set: load_dataset(..., keep_source=True) first")
+        if not (0 <= seed < 1 << 32 and 0 <= key < 1 << 32):
+            raise ValueError("shuffle seed and key must be in [0, 2^32)")
+        N, P = self.num_samples, self.P
+        if N == 0:
+            return
+        if self.backend == "hip":
+            ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
+            hip().mlp_shuffle(ptr(self.X0), ptr(self.labels0), ptr(self.X), ptr(self.labels), ptr(self.XT),
+                              ptr(self.Xs), ptr(self.Xw), ptr(self.XTw), ptr(self._perm), N, P,
+                              self.X.element_size(), seed, key, int(identity),
+                              torch.cuda.current_stream(self.device).cuda_stream)
+            self.shuffle_launches += 1
+            return
+        with torch.no_grad():
+            perm = (np.arange(N, dtype=np.int32) if identity else cpu().epoch_permutation(N, seed, key))
+            self._perm.copy_(torch.from_numpy(perm))
+            idx = self._perm.long()
+            self.X.copy_(self.X0.index_select(0, idx))
+            self.labels.copy_(self.labels0.index_select(0, idx))
+            if self.XT is not None:
+                self.XT[:P].copy_(self.X.t())
+            if self.Xs is not None:
+                self.Xs.copy_(fragment_order_pixels(self.X))
+            if self.Xw is not None:
+                self.Xw.copy_(self.X.to(torch.bfloat16))
+                self.XTw[:P].copy_(self.X.t().to(torch.bfloat16))
 
     def set_params(self, W1, b1, W2, b2):
         self.join()

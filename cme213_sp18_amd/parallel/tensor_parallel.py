@@ -45,8 +45,9 @@ class TensorParallelTrainer:
 
     def __init__(self, nn, comm: Communicator | None = None, device=None, dtype: str = "f32",
                  batch_size: int = 800, backend: str = "hip", shift: bool = True, normalize: bool = False,
-                 path: str = "auto", allreduce: str = "auto"):
+                 path: str = "auto", allreduce: str = "auto", shuffle_seed: int | None = None):
         self.nn = nn
+        self.shuffle_seed = None if shuffle_seed is None else int(shuffle_seed)  # (DataParallelTrainer's)
         self.comm = comm or NullComm()
         self.R, self.rank = self.comm.world_size, self.comm.rank
         P, H, C = nn.H
@@ -162,7 +163,8 @@ class TensorParallelTrainer:
 
     # -------------------------------------------------------------------- data
     def load(self, x_train, y_train):
-        self.engine.load_dataset(x_train, y_train, normalize=self.normalize)
+        self.engine.load_dataset(x_train, y_train, normalize=self.normalize,
+                                 keep_source=self.shuffle_seed is not None)
         self.N = self.engine.num_samples
 
     def epoch_plan(self, N: int | None = None) -> EpochPlan:
@@ -293,14 +295,18 @@ class TensorParallelTrainer:
 
     # ------------------------------------------------------------------- train
     def train(self, epochs: int, lr: float, reg: float, print_every: int = 0, debug: bool = False,
-              outdir: str = "Outputs", log=print, on_event=None, fault=None) -> TrainStats:
+              outdir: str = "Outputs", log=print, on_event=None, fault=None,
+              shuffle_seed: int | None = None) -> TrainStats:
         """Training loop with the data-parallel trainer's interface (loss every ``print_every`` steps,
         JSON-lines epoch events, ``fault=(rank, step)`` injection); graph-replayed epochs when no loss is
-        printed.  ``debug`` (the reference's per-iteration CPU diff) is data-parallel only."""
+        printed.  ``debug`` (the reference's per-iteration CPU diff) is data-parallel only.  ``shuffle_seed``
+        (default: the constructor's): the resident set -- whole on every rank -- is reordered on the device before
+        each epoch, as in DataParallelTrainer.train."""
         from .trainer import CommFailure, FaultInjected
 
         stats = TrainStats()
         plan = self.epoch_plan()
+        seed = self.shuffle_seed if shuffle_seed is None else int(shuffle_seed)
         dev = self.engine.device
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
@@ -309,6 +315,8 @@ class TensorParallelTrainer:
         for epoch in range(epochs):
             if fault is not None and fault[0] == self.rank and self.iter <= fault[1] < self.iter + len(plan.steps):
                 raise FaultInjected(f"injected fault on rank {self.rank} at step {fault[1]}")
+            if seed is not None:
+                self.engine.enqueue_shuffle(seed, self.iter)
             if print_every <= 0 and self.profiler is None:
                 self.run_plan(plan, lr, reg, use_graphs=self.use_graphs)
                 self.iter += len(plan.steps)

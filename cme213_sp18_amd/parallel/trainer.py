@@ -235,8 +235,12 @@ class DataParallelTrainer:
                  batch_size: int = 800, backend: str = "hip", shift: bool = True, use_graphs: bool = True,
                  normalize: bool = False, path: str = "auto", allreduce: str = "auto", overlap: bool = True,
                  overlap_chunks: int = 0, fuse_allreduce: bool = True, executor: str = "auto",
-                 grad_wire: str = "auto", fused_form: str = "auto"):
+                 grad_wire: str = "auto", fused_form: str = "auto", shuffle_seed: int | None = None):
         self.nn = nn
+        # per-epoch shuffle of the resident training set (None: the loaded order every epoch, nothing kept or
+        # launched): load() keeps the pristine rows and train() reorders every layout on the device before each
+        # epoch -- the order of the epoch that starts at iteration counter i is epoch_permutation(N, seed, i)
+        self.shuffle_seed = None if shuffle_seed is None else int(shuffle_seed)
         # how run_plan enqueues a plan: "auto" = the native C++ step loop (MlpStep.run_steps) for plans of
         # consecutive full batches on the fused paths (pure device work), else the captured HIP graph;
         # "graph" = always the graph; "eager" = Python step by step
@@ -510,7 +514,8 @@ class DataParallelTrainer:
 
     # ---------------------------------------------------------------- data
     def load(self, x_train, y_train):
-        self.engine.load_dataset(x_train, y_train, normalize=self.normalize)
+        self.engine.load_dataset(x_train, y_train, normalize=self.normalize,
+                                 keep_source=self.shuffle_seed is not None)
         self.N = self.engine.num_samples
         self._graphs.clear()
         if self._xgmi_fused is not None:
@@ -623,7 +628,8 @@ class DataParallelTrainer:
     def step(self, start: int, length: int, lr: float, reg: float, with_loss: bool = False,
              next_start: int = -1) -> None:
         """Enqueue one global SGD step on the current stream (no host sync).  next_start: this rank's first sample
-        of the next step (the fused paths prefetch its pixels; -1: unknown)."""
+        of the next step (the fused paths prefetch its pixels; -1: unknown).  ``start`` indexes the CURRENT order of
+        the resident set: after a shuffled train() that is the last epoch's order (engine.permutation())."""
         e = self.engine
         off, n = self.shard(start, length)
         if self.profiler is not None and n > 0:
@@ -879,7 +885,7 @@ class DataParallelTrainer:
     # ---------------------------------------------------------------- train
     def train(self, epochs: int, lr: float, reg: float, print_every: int = 0, debug: bool = False,
               outdir: str = "Outputs", log=print, on_event=None, fault: tuple[int, int] | None = None,
-              diff_file=None, eval_every: int = 0) -> TrainStats:
+              diff_file=None, eval_every: int = 0, shuffle_seed: int | None = None) -> TrainStats:
         """Full training loop (neural_network.cpp:446-555).  Eager steps where the
         host must look at a step (loss printing / debug diffs), graphs elsewhere.
 
@@ -899,12 +905,21 @@ class DataParallelTrainer:
         the epoch anyway (on_event, print_every, debug -- the same on every rank: the read is collective): then an
         {"event": "eval", ...} record without the matrix goes to on_event and rank 0 logs one line.
 
+        shuffle_seed (default: the constructor's; the set must have been loaded with a seed there, which keeps the
+        pristine rows): before every epoch the resident set is reordered on the device (engine.enqueue_shuffle(seed,
+        self.iter), one launch on the stream, no host work), on every executor and on the per-step path.  The order
+        depends on (seed, iteration counter at the epoch start) alone: a recovered epoch re-enqueues the same order,
+        train(2) + train(2) equals train(4), and a resumed run (``iter`` restored) continues the sequence.  Every rank
+        forms the same order from the same seed.  The validation set is never shuffled.  Afterwards the set stays in
+        the last epoch's order.
+
         With the xGMI all-reduce, every epoch ends with a collective check of the peer-wait error flag
         (assert_comm_ok): a timed-out wait raises CommFailure on every rank before another epoch runs."""
         from ..utils.checkpoint import write_diff_gpu_cpu
 
         stats = TrainStats()
         plan = self.epoch_plan()
+        seed = self.shuffle_seed if shuffle_seed is None else int(shuffle_seed)
         err_file, own_file = diff_file, False
         if debug and self.rank == 0 and err_file is None:  # only rank 0 owns the diff file
             os.makedirs(outdir, exist_ok=True)
@@ -949,6 +964,8 @@ class DataParallelTrainer:
                 raise FaultInjected(f"injected fault on rank {self.rank} at step {fault[1]}")
 
         def run_epoch(epoch: int) -> None:
+            if seed is not None:  # (inside run_epoch: a recovered epoch restores self.iter and gets the same order)
+                self.engine.enqueue_shuffle(seed, self.iter)
             if not host_needed:
                 maybe_fault(self.iter, len(plan.steps))
                 with self.roctx.range(f"epoch {epoch}"):

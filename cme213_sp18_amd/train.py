@@ -100,6 +100,9 @@ def run(cfg: TrainConfig) -> dict:
         if cfg.resume:
             nn, meta = load_checkpoint(cfg.resume)
             log0(rank, f"Resumed from {cfg.resume}: {meta}")
+            if meta.get("shuffle_seed") != cfg.shuffle_seed:
+                log0(rank, f"warning: the checkpoint was trained with --shuffle-seed {meta.get('shuffle_seed')}, this "
+                           f"run uses {cfg.shuffle_seed}: the epochs' orders do not continue the checkpoint's")
         else:
             nn = NeuralNetwork(cfg.H)
         seq_nn = nn.copy()
@@ -111,7 +114,7 @@ def run(cfg: TrainConfig) -> dict:
             t = time.perf_counter()
             mlp.train(seq_nn, xs, ds.y_train, cfg.learning_rate, cfg.reg, cfg.num_epochs, cfg.batch_size,
                       False, cfg.print_every, cfg.debug, cfg.outdir, cfg.softmax_shift, cfg.ckpt_precision,
-                      iter0=int(meta.get("iter", 0)))
+                      iter0=int(meta.get("iter", 0)), shuffle_seed=cfg.shuffle_seed)
             out["seq_seconds"] = time.perf_counter() - t
             log0(rank, f"Time for Sequential Training: {out['seq_seconds']:.6f} seconds")
             out["seq_dev_precision"] = precision(mlp.predict(seq_nn, xd, cfg.softmax_shift), ds.y_dev)
@@ -127,13 +130,13 @@ def run(cfg: TrainConfig) -> dict:
             tr = TensorParallelTrainer(nn, comm=comm, device=device, dtype=cfg.dtype, batch_size=cfg.batch_size,
                                        backend=backend, shift=cfg.softmax_shift, normalize=cfg.normalize,
                                        path=cfg.path,
-                                       allreduce=tp_allreduce_mode(cfg.allreduce))
+                                       allreduce=tp_allreduce_mode(cfg.allreduce), shuffle_seed=cfg.shuffle_seed)
             tr.use_graphs = cfg.use_graphs
         else:
             tr = DataParallelTrainer(nn, comm=comm, device=device, dtype=cfg.dtype, batch_size=cfg.batch_size,
                                      backend=backend, shift=cfg.softmax_shift, use_graphs=cfg.use_graphs,
                                      normalize=cfg.normalize, path=cfg.path, allreduce=cfg.allreduce,
-                                     overlap_chunks=cfg.overlap_chunks)
+                                     overlap_chunks=cfg.overlap_chunks, shuffle_seed=cfg.shuffle_seed)
         tr.load(ds.x_train, ds.y_train)
         eval_every = cfg.eval_every if cfg.parallel != "tp" else 0
         if cfg.eval_every > 0 and not eval_every:
@@ -148,7 +151,8 @@ def run(cfg: TrainConfig) -> dict:
             tr.enable_profiling()
         fault = parse_fault(cfg.fault_inject)
         ckpt_meta = lambda done: {"epochs": done + meta.get("epochs", 0), "lr": cfg.learning_rate, "reg": cfg.reg,
-                                  "seed": cfg.seed, "dtype": cfg.dtype, "iter": tr.iter}
+                                  "seed": cfg.seed, "dtype": cfg.dtype, "iter": tr.iter,
+                                  "shuffle_seed": cfg.shuffle_seed}
         seg = cfg.ckpt_every if (cfg.ckpt_every > 0 and cfg.ckpt_dir) else cfg.num_epochs
         done, st = 0, None
         while done < cfg.num_epochs or st is None:  # train in checkpoint segments

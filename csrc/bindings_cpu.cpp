@@ -10,6 +10,7 @@
 #include "cpu/io.h"
 #include "cpu/mlp_cpu.h"
 #include "cpu/suite_cpu.h"
+#include "mlp/shuffle.h"
 
 namespace py = pybind11;
 using f64arr = py::array_t<double, py::array::c_style | py::array::forcecast>;
@@ -134,6 +135,20 @@ PYBIND11_MODULE(_cpu, m) {
       py::arg("reg"), py::arg("epochs"), py::arg("batch"), py::arg("print_every") = 0, py::arg("debug") = false,
       py::arg("outdir") = "Outputs", py::arg("shift") = true, py::arg("ckpt_precision") = 12,
       py::arg("iter0") = 0);
+
+  // the per-epoch shuffle's order (csrc/mlp/shuffle.h, the header the gather kernel compiles): sample i of the
+  // shuffled set is source sample perm[i]; key = the iteration counter at the epoch start
+  m.def(
+      "epoch_permutation",
+      [](int64_t n, uint32_t seed, uint32_t key) {
+        if (n < 0 || n > INT32_MAX) throw std::invalid_argument("epoch_permutation: n must be in [0, 2^31)");
+        py::array_t<int32_t> out(n);
+        int32_t* o = out.mutable_data();
+        const uint64_t k = cme::shuffle_key(seed, key);
+        for (int64_t i = 0; i < n; ++i) o[i] = (int32_t)cme::shuffle_index((uint32_t)i, (uint32_t)n, k);
+        return out;
+      },
+      py::arg("n"), py::arg("seed"), py::arg("key"));
 
   // ---------------------------------------------------------------- I/O
   m.def(

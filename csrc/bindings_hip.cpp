@@ -14,6 +14,7 @@
 #include "mlp/mlp_kernels.h"
 #include "mlp/mlp_split.h"
 #include "mlp/mlp_step.h"
+#include "mlp/shuffle.h"
 #include "suite/suite_kernels.h"
 
 namespace py = pybind11;
@@ -279,6 +280,19 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       },
       py::arg("params"), py::arg("grads"), py::arg("count"), py::arg("lr"), py::arg("W1p"), py::arg("w1n"),
       py::arg("npw"), py::arg("stream") = 0, py::arg("status") = 0);
+  m.def(
+      "mlp_shuffle",
+      [](uintptr_t X0, uintptr_t labels0, uintptr_t X, uintptr_t labels, uintptr_t XT, uintptr_t Xs, uintptr_t Xw,
+         uintptr_t XTw, uintptr_t perm, int N, int Pd, int es, uint32_t seed, uint32_t key, int identity, uintptr_t s) {
+        cme::ShuffleArgs a;
+        a.X0 = P<const void>(X0); a.labels0 = P<const int>(labels0); a.X = P<void>(X); a.labels = P<int>(labels);
+        a.XT = P<void>(XT); a.Xs = P<void>(Xs); a.Xw = P<void>(Xw); a.XTw = P<void>(XTw); a.perm = P<int>(perm);
+        a.N = N; a.P = Pd; a.es = es; a.key = cme::shuffle_key(seed, key); a.identity = identity;
+        cme::mlp_shuffle(a, P<void>(s));
+      },
+      py::arg("X0"), py::arg("labels0"), py::arg("X"), py::arg("labels"), py::arg("XT"), py::arg("Xs"), py::arg("Xw"),
+      py::arg("XTw"), py::arg("perm"), py::arg("N"), py::arg("P"), py::arg("es"), py::arg("seed"), py::arg("key"),
+      py::arg("identity") = 0, py::arg("stream") = 0);
   m.def("mlp_split_fused_tiles", &cme::mlp_split_fused_tiles, py::arg("P"), py::arg("H"), py::arg("cap"));
 
   bind_suite(m);
