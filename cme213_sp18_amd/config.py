@@ -52,6 +52,19 @@ class TrainConfig:
     shuffle_seed: int | None = None  # --shuffle-seed S: reshuffle the resident training set on the device every epoch
     gpus: int = 0               # ranks (one per GPU); 0 = WORLD_SIZE of the launcher, else 1.  N > 1 without a
                                 # launcher: the CLI starts the N ranks itself (parallel/launcher.self_launch)
+    optimizer: str = "sgd"      # --optimizer sgd | momentum | adam (optim.Optimizer; sequential and parallel run alike)
+    momentum: float = 0.9       # --momentum
+    nesterov: bool = False      # --nesterov
+    beta1: float = 0.9          # --beta1
+    beta2: float = 0.999        # --beta2
+    adam_eps: float = 1e-8      # --adam-eps
+
+    @property
+    def optim(self):
+        from .optim import Optimizer
+
+        return Optimizer(self.optimizer, momentum=self.momentum, nesterov=self.nesterov, beta1=self.beta1,
+                         beta2=self.beta2, eps=self.adam_eps)
 
     @property
     def H(self):
@@ -128,6 +141,14 @@ def build_parser() -> argparse.ArgumentParser:
                     help="reshuffle the resident training set on the device before every epoch (sequential and "
                          "parallel run alike; the order depends on the seed and the iteration counter only, so "
                          "--resume continues the sequence); default: the loaded order every epoch")
+    ap.add_argument("--optimizer", choices=["sgd", "momentum", "adam"],
+                    help="the update rule (default sgd, the reference's w -= lr g); momentum and adam keep their state "
+                         "on the device and cost one extra launch per step (data parallel only)")
+    ap.add_argument("--momentum", type=float, help="momentum coefficient in [0, 1) (default 0.9)")
+    ap.add_argument("--nesterov", action="store_true", default=None, help="Nesterov momentum")
+    ap.add_argument("--beta1", type=float, help="Adam's first-moment decay (default 0.9)")
+    ap.add_argument("--beta2", type=float, help="Adam's second-moment decay (default 0.999)")
+    ap.add_argument("--adam-eps", type=float, help="Adam's epsilon (default 1e-8)")
     ap.add_argument("--gpus", type=int,
                     help="number of ranks, one per GPU (the reference's mpirun -np N); started here when no "
                          "launcher started this process")
@@ -137,7 +158,8 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def parse_config(argv=None) -> TrainConfig:
-    a = build_parser().parse_args(argv)
+    ap = build_parser()
+    a = ap.parse_args(argv)
     cfg = TrainConfig()
     explicit = {k: v for k, v in vars(a).items() if v is not None and k != "preset"}
     if a.preset:
@@ -156,4 +178,11 @@ def parse_config(argv=None) -> TrainConfig:
         # fp64 engine unless a dtype was requested explicitly
         if "dtype" not in explicit:
             cfg.dtype = "f64"
+    # refused here, before any data is loaded or the sequential run starts: TensorParallelTrainer applies plain SGD only
+    if cfg.parallel == "tp" and cfg.optimizer != "sgd":
+        ap.error(f"--parallel tp applies plain SGD only; --optimizer {cfg.optimizer} needs --parallel dp")
+    try:
+        cfg.optim  # the hyper-parameters' ranges (optim.Optimizer validates)
+    except ValueError as ex:
+        ap.error(str(ex))
     return cfg

@@ -108,8 +108,13 @@ def numgrad(nn: NeuralNetwork, X, labels, reg: float, shift: bool = True) -> Gra
 def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, epochs: int = 15,
           batch_size: int = 800, grad_check: bool = False, print_every: int = -1, debug: bool = False,
           outdir: str = "Outputs", shift: bool = True, ckpt_precision: int = 12, iter0: int = 0,
-          shuffle_seed: int | None = None) -> list[float]:
+          shuffle_seed: int | None = None, optimizer=None, optim_state: dict | None = None) -> list[float]:
     """Sequential fp64 minibatch SGD on the CPU -- the oracle (neural_network.cpp:219-279).
+
+    ``optimizer``: an ``optim.Optimizer`` (None or ``Optimizer.sgd()``: the reference's plain update).  A stateful
+    rule (momentum, Adam; csrc/mlp/optim.h) keeps its state in ``optim_state`` -- ``optim.new_state(optimizer,
+    nn.num_params())``, updated in place, so a later call (a resumed run, or one epoch at a time) continues it; None:
+    a fresh state for this call.
 
     ``iter0``: the iteration counter at the start -- a resumed run continues the loss / snapshot numbering.
 
@@ -132,17 +137,32 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
         ng = numgrad(nn, X[:n], labels[:n], reg, shift)
         if not gradcheck(ng, g):
             raise AssertionError("gradient check failed")
-    if shuffle_seed is None:
-        return list(cpu().train(*nn.params, X, labels, float(learning_rate), float(reg), int(epochs),
-                                int(batch_size), int(print_every), bool(debug), outdir, shift, int(ckpt_precision),
-                                int(iter0)))
-    losses: list[float] = []
-    n = X.shape[0]
-    it = int(iter0)
-    for _ in range(int(epochs)):
-        perm = cpu().epoch_permutation(n, int(shuffle_seed), it)
-        losses += cpu().train(*nn.params, np.ascontiguousarray(X[perm]), np.ascontiguousarray(labels[perm]),
-                              float(learning_rate), float(reg), 1, int(batch_size), int(print_every), bool(debug),
-                              outdir, shift, int(ckpt_precision), it)
-        it += (n + int(batch_size) - 1) // int(batch_size)
-    return losses
+    from ..optim import new_state, resolve
+
+    opt = resolve(optimizer)
+    kw = {}
+    if opt is not None:
+        st = optim_state if optim_state is not None else new_state(opt, nn.num_params())
+        if st["kind"] != opt.kind or any(s.size != nn.num_params() or s.dtype != np.float64 for s in st["state"]):
+            raise ValueError("optim_state does not belong to this optimizer and network")
+        counter = np.array([st["t"], st["b1p"], st["b2p"]], np.float64)
+        kw["optim"] = (opt.code, opt.hyper(learning_rate), st["state"][0],
+                       st["state"][1] if opt.num_state > 1 else None, counter)
+    try:
+        if shuffle_seed is None:
+            return list(cpu().train(*nn.params, X, labels, float(learning_rate), float(reg), int(epochs),
+                                    int(batch_size), int(print_every), bool(debug), outdir, shift,
+                                    int(ckpt_precision), int(iter0), **kw))
+        losses: list[float] = []
+        n = X.shape[0]
+        it = int(iter0)
+        for _ in range(int(epochs)):
+            perm = cpu().epoch_permutation(n, int(shuffle_seed), it)
+            losses += cpu().train(*nn.params, np.ascontiguousarray(X[perm]), np.ascontiguousarray(labels[perm]),
+                                  float(learning_rate), float(reg), 1, int(batch_size), int(print_every),
+                                  bool(debug), outdir, shift, int(ckpt_precision), it, **kw)
+            it += (n + int(batch_size) - 1) // int(batch_size)
+        return losses
+    finally:
+        if opt is not None:
+            st["t"], st["b1p"], st["b2p"] = int(counter[0]), float(counter[1]), float(counter[2])

@@ -167,6 +167,9 @@ class MlpEngine:
         self.lazy_planes = True
         self._ag_test_skip, self._ag_wait_us = -1, 50_000  # inject_handoff_timeout (tests); 50 ms default
         self.kpart = None  # split-K dW1 slabs (enable_splitk)
+        # the update rule of apply() (set_optimizer): None = plain SGD, no state; else the state buffers and the
+        # device-resident counter records of a stateful optimizer
+        self.optimizer, self.opt_bufs, self.opt_rec = None, [], None
 
     def _configure_path(self):
         dev = self.device
@@ -642,6 +645,103 @@ class MlpEngine:
             with torch.no_grad():
                 self.params.sub_(lr * self.grads)
                 self.refresh_shadow()
+
+    # ------------------------------------------------- stateful optimizers
+    def set_optimizer(self, opt) -> None:
+        """Select the update rule of apply().  None / Optimizer.sgd(): plain SGD, nothing allocated.  Momentum
+        allocates one arena-sized state buffer in the parameter dtype and Adam two, plus the counter records
+        {t, b1^t, b2^t, 0} (fp64; one per workgroup of the kernel's fixed grid on the hip backend, one otherwise) --
+        all zeroed / reset."""
+        from ..optim import resolve
+
+        self.optimizer = resolve(opt)
+        if self.optimizer is None:
+            self.opt_bufs, self.opt_rec = [], None
+            return
+        dev = self.device
+        self.opt_bufs = [torch.zeros(self.layout.total, dtype=self.pdt, device=dev)
+                         for _ in range(self.optimizer.num_state)]
+        nrec = int(hip().optim_grid(self.layout.total)) if self.backend == "hip" else 1
+        self.opt_rec = torch.zeros(nrec, 4, dtype=torch.float64, device=dev)
+        self.reset_optimizer()
+
+    def reset_optimizer(self) -> None:
+        """Zero the optimizer state and the update count."""
+        if self.optimizer is None:
+            return
+        with torch.no_grad():
+            for b in self.opt_bufs:
+                b.zero_()
+            self.opt_rec.copy_(torch.tensor([0.0, 1.0, 1.0, 0.0], dtype=torch.float64).expand_as(self.opt_rec))
+
+    def _unpadded(self, flat: torch.Tensor) -> np.ndarray:
+        return torch.cat([v.reshape(-1) for v in self.layout.views(flat)]).to("cpu", torch.float64).numpy().copy()
+
+    def optim_state(self) -> dict | None:
+        """Host copy of the optimizer state: {kind, t, b1p, b2p, state: [fp64 arrays over [W1|b1|W2|b2], unpadded]}
+        (the layout of optim.new_state and models.mlp.train); None for plain SGD.  Checks that every workgroup's
+        counter record agrees.  Synchronises."""
+        if self.optimizer is None:
+            return None
+        rec = self.opt_rec.cpu()
+        if not bool((rec == rec[0]).all()):
+            raise RuntimeError("optimizer counter records disagree: " + str(rec[:, :3].unique(dim=0).tolist()))
+        return {"kind": self.optimizer.kind, "t": int(rec[0, 0]), "b1p": float(rec[0, 1]), "b2p": float(rec[0, 2]),
+                "state": [self._unpadded(b) for b in self.opt_bufs]}
+
+    def set_optim_state(self, st: dict) -> None:
+        if self.optimizer is None:
+            raise RuntimeError("set_optimizer() with a stateful optimizer first")
+        if st["kind"] != self.optimizer.kind or len(st["state"]) != len(self.opt_bufs):
+            raise ValueError(f"the state is a {st['kind']} state, the optimizer is {self.optimizer.kind}")
+        srcs = [torch.as_tensor(np.asarray(s, np.float64)).reshape(-1) for s in st["state"]]
+        count = sum(v.numel() for v in self.layout.views(self.params))
+        if any(s.numel() != count for s in srcs):  # (before anything is copied)
+            raise ValueError(f"the state must hold one value per parameter ({count}), got "
+                             f"{[int(s.numel()) for s in srcs]}")
+        with torch.no_grad():
+            for buf, src in zip(self.opt_bufs, srcs):
+                o = 0
+                for v in self.layout.views(buf):
+                    v.copy_(src[o:o + v.numel()].view(v.shape).to(v.dtype))
+                    o += v.numel()
+            rec = torch.tensor([float(st["t"]), float(st["b1p"]), float(st["b2p"]), 0.0], dtype=torch.float64)
+            self.opt_rec.copy_(rec.expand_as(self.opt_rec))
+
+    def apply(self, lr: float) -> None:
+        """Apply the gradient bucket to the arena with the engine's update rule: sgd(lr) for plain SGD, else ONE
+        launch of the stateful kernel (csrc/mlp/optim.hip), which also refreshes the bf16 planes / shadow of W1,
+        advances the device-resident update count and applies nothing when the bucket's status element is non-zero.
+        No host sync: legal under stream capture."""
+        if self.optimizer is None:
+            self.sgd(lr)
+            return
+        o = self.optimizer
+        self._w1_written()
+        if self.backend == "hip":
+            planes, np_ = (self.W1p, self.np) if self.np else ((self.W1g, 1) if self.dtype == "bf16" else (None, 0))
+            hip().optim_step(0 if self.pdt == torch.float32 else 1, o.code, *o.hyper(lr), self.params.data_ptr(),
+                             self.grads.data_ptr(), self.opt_bufs[0].data_ptr(),
+                             self.opt_bufs[1].data_ptr() if len(self.opt_bufs) > 1 else 0, self.layout.total,
+                             planes.data_ptr() if planes is not None else 0, np_, self.H * self.P if np_ else 0,
+                             self.grads[self.status_index:].data_ptr(), self.opt_rec.data_ptr(),
+                             int(self.opt_rec.shape[0]), torch.cuda.current_stream(self.device).cuda_stream)
+            return
+        with torch.no_grad():
+            if float(self.grads[self.status_index]) != 0.0:
+                return
+            host = self.device.type == "cpu"
+            arrs = [t if host else t.cpu() for t in (self.params, self.grads, *self.opt_bufs)]
+            rec = self.opt_rec[0].cpu()
+            t, b1p, b2p = cpu().optim_step(o.code, o.hyper(lr), *(a.numpy() for a in arrs[:3]),
+                                           arrs[3].numpy() if len(arrs) > 3 else None, int(rec[0]), float(rec[1]),
+                                           float(rec[2]))
+            if not host:
+                for dst, src in zip((self.params, None, *self.opt_bufs), arrs):
+                    if dst is not None:
+                        dst.copy_(src)
+            self.opt_rec.copy_(torch.tensor([float(t), b1p, b2p, 0.0], dtype=torch.float64).expand_as(self.opt_rec))
+            self.refresh_shadow()
 
     def reg_only_grads(self, reg: float):
         """Gradient of an EMPTY shard: reg*W for weights, 0 for biases (the

@@ -45,7 +45,14 @@ class TensorParallelTrainer:
 
     def __init__(self, nn, comm: Communicator | None = None, device=None, dtype: str = "f32",
                  batch_size: int = 800, backend: str = "hip", shift: bool = True, normalize: bool = False,
-                 path: str = "auto", allreduce: str = "auto", shuffle_seed: int | None = None):
+                 path: str = "auto", allreduce: str = "auto", shuffle_seed: int | None = None, optimizer=None):
+        from ..optim import resolve
+
+        # the shard's update stays inside its weight-gradient launch (plain SGD); the stateful rules are
+        # data-parallel only for now
+        if resolve(optimizer) is not None:
+            raise ValueError(f"tensor parallelism applies plain SGD only (got optimizer {optimizer.kind!r}); "
+                             "use data parallelism (--parallel dp) for momentum or Adam")
         self.nn = nn
         self.shuffle_seed = None if shuffle_seed is None else int(shuffle_seed)  # (DataParallelTrainer's)
         self.comm = comm or NullComm()

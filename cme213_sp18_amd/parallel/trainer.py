@@ -235,8 +235,17 @@ class DataParallelTrainer:
                  batch_size: int = 800, backend: str = "hip", shift: bool = True, use_graphs: bool = True,
                  normalize: bool = False, path: str = "auto", allreduce: str = "auto", overlap: bool = True,
                  overlap_chunks: int = 0, fuse_allreduce: bool = True, executor: str = "auto",
-                 grad_wire: str = "auto", fused_form: str = "auto", shuffle_seed: int | None = None):
+                 grad_wire: str = "auto", fused_form: str = "auto", shuffle_seed: int | None = None,
+                 optimizer=None):
         self.nn = nn
+        # the update rule (optim.Optimizer): None / Optimizer.sgd() = the plain-SGD code as it stands.  A stateful
+        # rule (momentum, Adam) runs every step in gradient mode followed by engine.apply() -- one extra launch --
+        # on every sync path; the fused forms (the update inside the weight-gradient launch, the fused xGMI
+        # all-reduce, the native step loop) apply plain SGD only and are not taken (native_reason says so)
+        from ..optim import resolve
+
+        self.optimizer = resolve(optimizer)
+        self.native_reason = ""  # why native_plan() last returned None for a reason of the optimizer's
         # per-epoch shuffle of the resident training set (None: the loaded order every epoch, nothing kept or
         # launched): load() keeps the pristine rows and train() reorders every layout on the device before each
         # epoch -- the order of the epoch that starts at iteration counter i is epoch_permutation(N, seed, i)
@@ -278,6 +287,7 @@ class DataParallelTrainer:
         self.engine = MlpEngine(nn.H, dtype=dtype, max_cols=max_cols, device=device, backend=backend, shift=shift,
                                 path=path)
         self.engine.set_params(*nn.params)
+        self.engine.set_optimizer(self.optimizer)
         # training reads nothing of a1 after a step: the wide fused forward + head launch skips its 13 MB store
         # at H = 4096 (bench/wide_ag_ab.py: -1.4 us/step fp32, -2.1 us bf16)
         self.engine.set_store_a1(False)
@@ -305,7 +315,7 @@ class DataParallelTrainer:
         self._xgmi_fused = None
         self.fused_allreduce = False
         if (self.xgmi is not None and fuse_allreduce and self.xgmi.wire == self.engine.params.dtype
-                and self.xgmi.shots == 1):
+                and self.xgmi.shots == 1 and self.optimizer is None):
             slots = self.engine.fused_allreduce_slots()
             if self.fused_form == "auto":
                 self.fused_form = "pull"
@@ -445,10 +455,14 @@ class DataParallelTrainer:
         show up here as a mismatch rather than as a hang."""
         if self.R == 1:
             return True
-        p = self.engine.params.detach().reshape(-1)
-        w = p.view(torch.int32) if p.element_size() == 4 else p.view(torch.int16) if p.element_size() == 2 \
-            else p.view(torch.int64)
-        w = w.to(torch.int64)
+        e = self.engine
+        p = e.params.detach().reshape(-1)
+        as_words = lambda t: t.view(torch.int32) if t.element_size() == 4 else t.view(torch.int16) \
+            if t.element_size() == 2 else t.view(torch.int64)  # noqa: E731
+        w = as_words(p).to(torch.int64)
+        if e.optimizer is not None:  # ... and the same optimizer state and update count
+            w = torch.cat([w] + [as_words(b.detach().reshape(-1)).to(torch.int64) for b in e.opt_bufs]
+                          + [e.opt_rec[0].view(torch.int64)])
         idx = torch.arange(1, w.numel() + 1, device=w.device, dtype=torch.int64)
         # two position-weighted sums, folded below 2^52 so they travel exactly as float64
         h = [int(w.sum().item()) % (1 << 52), int(((w % 65521) * (idx % 65519)).sum().item()) % (1 << 52)]
@@ -498,11 +512,15 @@ class DataParallelTrainer:
                 g = e.grads.cpu()
                 dist.all_reduce(g, group=self._host_group)
                 e.grads.copy_(g)
-            e.sgd(lr)
+            e.apply(lr)
             return
         if self.xgmi is None:
             self.comm.allreduce_(e.grads)
-            e.sgd(lr)
+            e.apply(lr)
+            return
+        if self.optimizer is not None:  # the separate xGMI all-reduce, then the stateful launch
+            self.xgmi.allreduce_(e.grads)
+            e.apply(lr)
             return
         planes, np_ = None, 0
         if e.np:  # split paths: refresh the exact bf16 planes of W1
@@ -640,7 +658,10 @@ class DataParallelTrainer:
             self._allreduce_sgd(lr)
             return
         scale = 1.0 / (n * self.R)
-        if isinstance(self.comm, NullComm) and self.allreduce_mode != "host":  # 1 process: SGD fused into wgrad
+        if self.optimizer is not None and isinstance(self.comm, NullComm) and self.allreduce_mode != "host":
+            e.run(off, n, scale, reg, lr, sgd=False, with_loss=with_loss)  # 1 process: gradient mode + apply
+            e.apply(lr)
+        elif isinstance(self.comm, NullComm) and self.allreduce_mode != "host":  # 1 process: SGD fused into wgrad
             e.run(off, n, scale, reg, lr, sgd=True, with_loss=with_loss, pf_next=next_start)
         elif self.fused_allreduce:
             e.run(off, n, scale, reg / self.R, lr, sgd=2, with_loss=with_loss, pf_next=next_start)
@@ -653,7 +674,7 @@ class DataParallelTrainer:
     def _profiled_step(self, off, n, scale, reg, lr, with_loss):
         """The same step, split into timed phases (PhaseTimer events + roctx ranges; eager only)."""
         e, P = self.engine, self.profiler
-        single = isinstance(self.comm, NullComm) and self.allreduce_mode != "host"
+        single = isinstance(self.comm, NullComm) and self.allreduce_mode != "host" and self.optimizer is None
         if e.backend != "hip":
             with P.phase("step"):
                 if single:
@@ -682,7 +703,7 @@ class DataParallelTrainer:
         with P.phase("allreduce"):
             self.comm.allreduce_(e.grads)
         with P.phase("sgd"):
-            e.sgd(lr)
+            e.apply(lr)
 
     def enable_profiling(self, roctx: bool = True):
         """Per-phase timing (and roctx ranges) for the following train() calls: steps run eagerly and
@@ -727,7 +748,7 @@ class DataParallelTrainer:
             with torch.cuda.stream(cs):
                 self.comm.allreduce_(view)
         cur.wait_stream(cs)
-        e.sgd(lr)
+        e.apply(lr)
 
     def step_loss(self, start: int, length: int, lr: float, reg: float) -> float:
         """One step that also returns the (pre-update) global loss -- reference
@@ -744,8 +765,11 @@ class DataParallelTrainer:
     def _snapshot(self):
         e = self.engine
         e.join()
-        return (e.params.clone(), (e.W1g.clone() if e.W1g is not e.W1 else None),
+        snap = (e.params.clone(), (e.W1g.clone() if e.W1g is not e.W1 else None),
                 (e.W1p.clone() if e.W1p is not None else None))
+        if e.optimizer is not None:  # the state buffers and every workgroup's counter record
+            snap += ([b.clone() for b in e.opt_bufs], e.opt_rec.clone())
+        return snap
 
     def _restore(self, snap):
         e = self.engine
@@ -754,11 +778,16 @@ class DataParallelTrainer:
             e.W1g.copy_(snap[1])
         if snap[2] is not None:
             e.W1p.copy_(snap[2])
+        if len(snap) > 3:
+            for b, src in zip(e.opt_bufs, snap[3]):
+                b.copy_(src)
+            e.opt_rec.copy_(snap[4])
         e.mark_planes_stale()
 
     def capture(self, plan: EpochPlan, lr: float, reg: float) -> torch.cuda.CUDAGraph:
         """Capture every step of ``plan`` into one HIP graph (state-neutral warm-up first)."""
-        key = (tuple(plan.steps), float(lr), float(reg))
+        key = (tuple(plan.steps), float(lr), float(reg)) + (
+            (self.optimizer.key(),) if self.optimizer is not None else ())
         g = self._graphs.get(key)
         if g is not None:
             return g
@@ -783,6 +812,12 @@ class DataParallelTrainer:
         a fused step (one process, or the xGMI all-reduce fused into wgrad) and consecutive full global
         batches (wrapping to 0 at the end of the dataset); else None."""
         e = self.engine
+        if self.optimizer is not None:
+            self.native_reason = (f"stateful optimizer ({self.optimizer.kind}): every step runs in gradient mode "
+                                  "followed by the optimizer launch")
+            if e.backend == "hip":
+                e._hip_step().xstep_reason = self.native_reason
+            return None
         if (self.executor != "auto" or e.backend != "hip" or self.profiler is not None or not plan.steps
                 or not ((isinstance(self.comm, NullComm) and self.allreduce_mode != "host") or self.fused_allreduce)):
             return None

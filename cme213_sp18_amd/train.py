@@ -14,6 +14,7 @@ Grade 4 runs the GEMM benchmark instead.
 """
 from __future__ import annotations
 
+import copy
 import json
 import os
 import sys
@@ -59,9 +60,10 @@ def run(cfg: TrainConfig) -> dict:
 
     from .models import mlp
     from .models.mlp import NeuralNetwork
+    from .optim import Optimizer
     from .parallel.launcher import PlacementError, init_distributed, shutdown, verify_placement
     from .parallel.trainer import DataParallelTrainer
-    from .utils.checkpoint import checkNNErrors, load_checkpoint, save_checkpoint
+    from .utils.checkpoint import checkNNErrors, load_checkpoint, load_optim_state, save_checkpoint
     from .utils.common import precision, save_label
     from .utils.data import load_dataset
 
@@ -97,9 +99,20 @@ def run(cfg: TrainConfig) -> dict:
                    f"test {ds.x_test.shape[0]} ({time.perf_counter() - t:.2f}s)")
         os.makedirs(cfg.outdir, exist_ok=True)
         meta = {}
+        opt = cfg.optim
+        opt_state = None  # the checkpoint's optimizer state (both runs continue it)
         if cfg.resume:
             nn, meta = load_checkpoint(cfg.resume)
             log0(rank, f"Resumed from {cfg.resume}: {meta}")
+            saved = Optimizer.from_meta(meta.get("optimizer"))  # (no record: plain SGD)
+            same = saved == opt if opt.stateful else not saved.stateful
+            if opt.stateful and same:
+                opt_state = load_optim_state(cfg.resume, meta)
+            if not same:
+                log0(rank, f"warning: the checkpoint was trained with optimizer {saved}, this run uses {opt}: the "
+                           "optimizer state starts fresh")
+            elif opt.stateful and opt_state is None:
+                log0(rank, "warning: the checkpoint holds no optimizer state (optim.npz): it starts fresh")
             if meta.get("shuffle_seed") != cfg.shuffle_seed:
                 log0(rank, f"warning: the checkpoint was trained with --shuffle-seed {meta.get('shuffle_seed')}, this "
                            f"run uses {cfg.shuffle_seed}: the epochs' orders do not continue the checkpoint's")
@@ -114,7 +127,8 @@ def run(cfg: TrainConfig) -> dict:
             t = time.perf_counter()
             mlp.train(seq_nn, xs, ds.y_train, cfg.learning_rate, cfg.reg, cfg.num_epochs, cfg.batch_size,
                       False, cfg.print_every, cfg.debug, cfg.outdir, cfg.softmax_shift, cfg.ckpt_precision,
-                      iter0=int(meta.get("iter", 0)), shuffle_seed=cfg.shuffle_seed)
+                      iter0=int(meta.get("iter", 0)), shuffle_seed=cfg.shuffle_seed, optimizer=opt,
+                      optim_state=copy.deepcopy(opt_state))
             out["seq_seconds"] = time.perf_counter() - t
             log0(rank, f"Time for Sequential Training: {out['seq_seconds']:.6f} seconds")
             out["seq_dev_precision"] = precision(mlp.predict(seq_nn, xd, cfg.softmax_shift), ds.y_dev)
@@ -130,13 +144,16 @@ def run(cfg: TrainConfig) -> dict:
             tr = TensorParallelTrainer(nn, comm=comm, device=device, dtype=cfg.dtype, batch_size=cfg.batch_size,
                                        backend=backend, shift=cfg.softmax_shift, normalize=cfg.normalize,
                                        path=cfg.path,
-                                       allreduce=tp_allreduce_mode(cfg.allreduce), shuffle_seed=cfg.shuffle_seed)
+                                       allreduce=tp_allreduce_mode(cfg.allreduce), shuffle_seed=cfg.shuffle_seed,
+                                       optimizer=opt)
             tr.use_graphs = cfg.use_graphs
         else:
             tr = DataParallelTrainer(nn, comm=comm, device=device, dtype=cfg.dtype, batch_size=cfg.batch_size,
                                      backend=backend, shift=cfg.softmax_shift, use_graphs=cfg.use_graphs,
                                      normalize=cfg.normalize, path=cfg.path, allreduce=cfg.allreduce,
-                                     overlap_chunks=cfg.overlap_chunks, shuffle_seed=cfg.shuffle_seed)
+                                     overlap_chunks=cfg.overlap_chunks, shuffle_seed=cfg.shuffle_seed, optimizer=opt)
+            if opt_state is not None:
+                tr.engine.set_optim_state(opt_state)
         tr.load(ds.x_train, ds.y_train)
         eval_every = cfg.eval_every if cfg.parallel != "tp" else 0
         if cfg.eval_every > 0 and not eval_every:
@@ -152,7 +169,9 @@ def run(cfg: TrainConfig) -> dict:
         fault = parse_fault(cfg.fault_inject)
         ckpt_meta = lambda done: {"epochs": done + meta.get("epochs", 0), "lr": cfg.learning_rate, "reg": cfg.reg,
                                   "seed": cfg.seed, "dtype": cfg.dtype, "iter": tr.iter,
-                                  "shuffle_seed": cfg.shuffle_seed}
+                                  "shuffle_seed": cfg.shuffle_seed,
+                                  **({"optimizer": opt.as_meta()} if opt.stateful else {})}
+        ckpt_optim = lambda: tr.engine.optim_state() if opt.stateful else None  # noqa: E731
         seg = cfg.ckpt_every if (cfg.ckpt_every > 0 and cfg.ckpt_dir) else cfg.num_epochs
         done, st = 0, None
         while done < cfg.num_epochs or st is None:  # train in checkpoint segments
@@ -169,7 +188,7 @@ def run(cfg: TrainConfig) -> dict:
             done += k
             if cfg.ckpt_dir and done < cfg.num_epochs:
                 if rank == 0:
-                    save_checkpoint(nn, cfg.ckpt_dir, meta=ckpt_meta(done))
+                    save_checkpoint(nn, cfg.ckpt_dir, meta=ckpt_meta(done), optim_state=ckpt_optim())
                     jlog({"event": "checkpoint", "dir": cfg.ckpt_dir, "epochs": done})
                 comm.barrier()
             if k == 0:
@@ -194,7 +213,7 @@ def run(cfg: TrainConfig) -> dict:
             if ds.y_test is not None:
                 out["par_test_precision"] = precision(pred, ds.y_test)
             if cfg.ckpt_dir:
-                save_checkpoint(nn, cfg.ckpt_dir, meta=ckpt_meta(cfg.num_epochs))
+                save_checkpoint(nn, cfg.ckpt_dir, meta=ckpt_meta(cfg.num_epochs), optim_state=ckpt_optim())
             if (cfg.grade or cfg.debug) and cfg.run_seq:
                 log0(rank, "\nGrading mode on. Checking for correctness")
                 out["correct"] = checkNNErrors(seq_nn, nn, os.path.join(cfg.outdir, "NNErrors.txt"))

@@ -128,17 +128,39 @@ def checkNNErrors(seq_nn, par_nn, path: str = "Outputs/NNErrors.txt", verbose: b
 
 
 def save_checkpoint(nn, directory: str, meta: dict | None = None, precision: int = 17,
-                    binary: bool = True) -> None:
-    """Resume checkpoint: W0/W1/b0/b1 raw_ascii (exact fp64 by default) + JSON sidecar (+ .npz)."""
+                    binary: bool = True, optim_state: dict | None = None) -> None:
+    """Resume checkpoint: W0/W1/b0/b1 raw_ascii (exact fp64 by default) + JSON sidecar (+ .npz).
+
+    ``optim_state`` (MlpEngine.optim_state(); None for plain SGD): the optimizer's state buffers go to ``optim.npz``
+    (fp64, [W1|b1|W2|b2] unpadded, with the running products b1^t, b2^t) and the sidecar records ``optim_kind`` and the
+    update count ``optim_t``; a stale optim.npz of an earlier run is removed otherwise."""
     os.makedirs(directory, exist_ok=True)
     for name, m in zip(_NAMES, _mats(nn)):
         save_raw_ascii(os.path.join(directory, f"{name}.mat"), m, precision)
     if binary:
         np.savez(os.path.join(directory, "params.npz"), W0=nn.W[0], W1=nn.W[1], b0=nn.b[0], b1=nn.b[1])
     m = dict(meta or {})
+    onpz = os.path.join(directory, "optim.npz")
+    if optim_state is not None:
+        np.savez(onpz, prods=np.array([optim_state["b1p"], optim_state["b2p"]], np.float64),
+                 **{f"s{i}": np.asarray(s, np.float64) for i, s in enumerate(optim_state["state"])})
+        m["optim_kind"], m["optim_t"] = optim_state["kind"], int(optim_state["t"])
+    elif os.path.exists(onpz):
+        os.remove(onpz)
     m["H"] = list(nn.H)
     with open(os.path.join(directory, "meta.json"), "w") as f:
         json.dump(m, f, indent=1, sort_keys=True)
+
+
+def load_optim_state(directory: str, meta: dict) -> dict | None:
+    """The optimizer state a checkpoint holds (the dict of MlpEngine.optim_state()), or None (plain SGD)."""
+    path = os.path.join(directory, "optim.npz")
+    if "optim_kind" not in meta or not os.path.exists(path):
+        return None
+    with np.load(path, allow_pickle=False) as z:
+        k = len([n for n in z.files if n.startswith("s")])
+        return {"kind": meta["optim_kind"], "t": int(meta["optim_t"]), "b1p": float(z["prods"][0]),
+                "b2p": float(z["prods"][1]), "state": [z[f"s{i}"].copy() for i in range(k)]}
 
 
 def load_checkpoint(directory: str):

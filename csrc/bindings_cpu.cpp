@@ -32,6 +32,16 @@ cme::cpu::NetView view(py::array_t<double>& W1, py::array_t<double>& b1, py::arr
   return v;
 }
 
+// (lr, mu, nesterov, beta1, beta2, eps) -> the update rules' hyper-parameters (mlp/optim.h)
+cme::OptimHyper hyper_of(py::handle h) {
+  const py::tuple t = h.cast<py::tuple>();
+  if (t.size() != 6) throw std::invalid_argument("hyper = (lr, mu, nesterov, beta1, beta2, eps)");
+  cme::OptimHyper o;
+  o.lr = t[0].cast<double>(); o.mu = t[1].cast<double>(); o.nesterov = t[2].cast<bool>() ? 1 : 0;
+  o.beta1 = t[3].cast<double>(); o.beta2 = t[4].cast<double>(); o.eps = t[5].cast<double>();
+  return o;
+}
+
 void check_x(const f64arr& X, int P) {
   if (X.ndim() != 2 || X.shape(1) != P) throw std::invalid_argument("X must be [n][P] float64");
 }
@@ -118,23 +128,105 @@ PYBIND11_MODULE(_cpu, m) {
       "train",
       [](py::array_t<double> W1, py::array_t<double> b1, py::array_t<double> W2, py::array_t<double> b2, f64arr X,
          i32arr labels, double lr, double reg, int epochs, int batch, int print_every, bool debug,
-         std::string outdir, bool shift, int ckpt_precision, int iter0) {
+         std::string outdir, bool shift, int ckpt_precision, int iter0, py::object optim) {
         auto v = view(W1, b1, W2, b2);
         check_x(X, v.P);
         cme::cpu::TrainOpts o;
         o.lr = lr; o.reg = reg; o.epochs = epochs; o.batch = batch; o.print_every = print_every;
         o.debug = debug; o.outdir = outdir; o.shift = shift; o.ckpt_precision = ckpt_precision; o.iter0 = iter0;
+        // optim: None, or (kind, hyper, s1, s2 | None, counter): the state arrays (float64, H P + H + C H + C) and
+        // the counter array {t, b1^t, b2^t} are updated in place
+        cme::OptimCounter ctr;
+        py::array_t<double> counter;
+        if (!optim.is_none()) {
+          const py::tuple t = optim.cast<py::tuple>();
+          if (t.size() != 5) throw std::invalid_argument("train: optim = (kind, hyper, s1, s2, counter)");
+          o.optim_kind = t[0].cast<int>();
+          o.hyper = hyper_of(t[1]);
+          const int64_t total = (int64_t)v.H * v.P + v.H + (int64_t)v.C * v.H + v.C;
+          auto state = [&](py::handle h) {
+            if (!py::isinstance<py::array_t<double>>(h)) throw std::invalid_argument("train: float64 state expected");
+            auto a = h.cast<py::array_t<double>>();
+            if (a.size() != total) throw std::invalid_argument("train: optimizer state must hold every parameter");
+            return mut(a);
+          };
+          o.s1 = state(t[2]);
+          if (!t[3].is_none()) o.s2 = state(t[3]);
+          if (!py::isinstance<py::array_t<double>>(t[4])) throw std::invalid_argument("train: float64 counter expected");
+          counter = t[4].cast<py::array_t<double>>();
+          if (counter.size() < 3) throw std::invalid_argument("train: the counter holds {t, b1^t, b2^t}");
+          const double* c = mut(counter);
+          ctr = {c[0], c[1], c[2]};
+          o.counter = &ctr;
+        }
         std::vector<double> losses;
         {
           py::gil_scoped_release r;
           losses = cme::cpu::train(v, X.data(), labels.data(), (int)X.shape(0), o);
+        }
+        if (o.counter) {
+          double* c = mut(counter);
+          c[0] = ctr.t; c[1] = ctr.b1p; c[2] = ctr.b2p;
         }
         return losses;
       },
       py::arg("W1"), py::arg("b1"), py::arg("W2"), py::arg("b2"), py::arg("X"), py::arg("labels"), py::arg("lr"),
       py::arg("reg"), py::arg("epochs"), py::arg("batch"), py::arg("print_every") = 0, py::arg("debug") = false,
       py::arg("outdir") = "Outputs", py::arg("shift") = true, py::arg("ckpt_precision") = 12,
-      py::arg("iter0") = 0);
+      py::arg("iter0") = 0, py::arg("optim") = py::none());
+
+  // one update of the stateful rules (csrc/mlp/optim.h, the header the kernel compiles) on float32 or float64 arrays,
+  // in place: kind 0 = momentum / Nesterov (s1 = v), 1 = adam (s1 = m, s2 = s); hyper = (lr, mu, nesterov, beta1,
+  // beta2, eps); t = the updates applied so far, b1p / b2p the running products b1^t, b2^t (None: formed by t
+  // multiplications).  Returns the advanced (t, b1p, b2p).
+  m.def(
+      "optim_step",
+      [](int kind, py::object hyper, py::array params, py::array grads, py::array s1, py::object s2, int64_t t,
+         py::object b1p, py::object b2p) {
+        const cme::OptimHyper h = hyper_of(hyper);
+        if (kind != cme::kMomentum && kind != cme::kAdam) throw std::invalid_argument("optim_step: kind 0 or 1");
+        cme::OptimCounter c;
+        if (b1p.is_none() || b2p.is_none()) {
+          for (int64_t i = 0; i < t; ++i) cme::optim_advance(c, h);
+        } else {
+          c = {(double)t, b1p.cast<double>(), b2p.cast<double>()};
+        }
+        cme::optim_advance(c, h);
+        const bool f32 = params.dtype().is(py::dtype::of<float>());
+        if (!f32 && !params.dtype().is(py::dtype::of<double>()))
+          throw std::invalid_argument("optim_step: float32 or float64 arrays expected");
+        std::vector<py::array> arrs = {params, grads, s1};
+        if (kind == cme::kAdam) {
+          if (s2.is_none()) throw std::invalid_argument("optim_step: adam needs s2");
+          arrs.push_back(s2.cast<py::array>());
+        }
+        const py::ssize_t n = params.size();
+        for (size_t k = 0; k < arrs.size(); ++k) {
+          const auto& a = arrs[k];
+          if (!a.dtype().is(params.dtype()) || a.size() != n || !(a.flags() & py::array::c_style) ||
+              (k != 1 && !a.writeable()))
+            throw std::invalid_argument("optim_step: arrays of one dtype and size, C-contiguous and writable, expected");
+        }
+        auto run = [&](auto tag) {
+          using T = decltype(tag);
+          T* p = static_cast<T*>(arrs[0].mutable_data());
+          const T* g = static_cast<const T*>(arrs[1].data());
+          T* a = static_cast<T*>(arrs[2].mutable_data());
+          if (kind == cme::kMomentum) {
+            const auto k = cme::momentum_coef<T>(h);
+            for (py::ssize_t i = 0; i < n; ++i) cme::momentum_update(p[i], a[i], g[i], k);
+          } else {
+            T* b = static_cast<T*>(arrs[3].mutable_data());
+            const auto k = cme::adam_coef<T>(h, c);
+            for (py::ssize_t i = 0; i < n; ++i) cme::adam_update(p[i], a[i], b[i], g[i], k);
+          }
+        };
+        if (f32) run(float{});
+        else run(double{});
+        return py::make_tuple((int64_t)c.t, c.b1p, c.b2p);
+      },
+      py::arg("kind"), py::arg("hyper"), py::arg("params"), py::arg("grads"), py::arg("s1"), py::arg("s2") = py::none(),
+      py::arg("t") = 0, py::arg("b1p") = py::none(), py::arg("b2p") = py::none());
 
   // the per-epoch shuffle's order (csrc/mlp/shuffle.h, the header the gather kernel compiles): sample i of the
   // shuffled set is source sample perm[i]; key = the iteration counter at the epoch start

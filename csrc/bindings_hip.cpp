@@ -14,6 +14,7 @@
 #include "mlp/mlp_kernels.h"
 #include "mlp/mlp_split.h"
 #include "mlp/mlp_step.h"
+#include "mlp/optim.h"
 #include "mlp/shuffle.h"
 #include "suite/suite_kernels.h"
 
@@ -208,7 +209,8 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       .def_readwrite("xstep", &MlpStep::xstep)
       .def_readwrite("xstep_pix", &MlpStep::xstep_pix)
       .def_readonly("xstep_used", &MlpStep::xstep_used)
-      .def_readonly("xstep_reason", &MlpStep::xstep_reason)
+      // (writable: a trainer that never enters run_steps -- a stateful optimizer -- records why here)
+      .def_readwrite("xstep_reason", &MlpStep::xstep_reason)
       .def_readwrite("xs_stamps", &MlpStep::xs_stamps)
       .def_readwrite("xs_stamp_steps", &MlpStep::xs_stamp_steps)
       .def_readwrite("xs_w1stamps", &MlpStep::xs_w1stamps)
@@ -294,6 +296,26 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       py::arg("XTw"), py::arg("perm"), py::arg("N"), py::arg("P"), py::arg("es"), py::arg("seed"), py::arg("key"),
       py::arg("identity") = 0, py::arg("stream") = 0);
   m.def("mlp_split_fused_tiles", &cme::mlp_split_fused_tiles, py::arg("P"), py::arg("H"), py::arg("cap"));
+  // the stateful optimizer step (csrc/mlp/optim.h): kind 0 = momentum / Nesterov, 1 = adam; rec = optim_grid(count)
+  // records of 4 doubles {t, b1^t, b2^t, 0}
+  m.def("optim_grid", &cme::optim_grid, py::arg("count"));
+  m.def(
+      "optim_step",
+      [](int dt, int kind, double lr, double mu, int nesterov, double beta1, double beta2, double eps,
+         uintptr_t params, uintptr_t grads, uintptr_t s1, uintptr_t s2, int64_t count, uintptr_t planes, int np,
+         int64_t w1n, uintptr_t status, uintptr_t rec, int nrec, uintptr_t s) {
+        cme::OptimArgs a;
+        a.dtype = dt; a.kind = kind;
+        a.h.lr = lr; a.h.mu = mu; a.h.nesterov = nesterov; a.h.beta1 = beta1; a.h.beta2 = beta2; a.h.eps = eps;
+        a.params = P<void>(params); a.grads = P<const void>(grads); a.s1 = P<void>(s1); a.s2 = P<void>(s2);
+        a.count = count; a.planes = P<void>(planes); a.np = np; a.w1n = w1n; a.status = P<const void>(status);
+        a.rec = P<double>(rec); a.nrec = nrec;
+        cme::mlp_optim_step(a, P<void>(s));
+      },
+      py::arg("dt"), py::arg("kind"), py::arg("lr"), py::arg("mu"), py::arg("nesterov"), py::arg("beta1"),
+      py::arg("beta2"), py::arg("eps"), py::arg("params"), py::arg("grads"), py::arg("s1"), py::arg("s2"),
+      py::arg("count"), py::arg("planes") = 0, py::arg("np") = 0, py::arg("w1n") = 0, py::arg("status") = 0,
+      py::arg("rec") = 0, py::arg("nrec") = 0, py::arg("stream") = 0);
 
   bind_suite(m);
   bind_comm(m);

@@ -174,6 +174,8 @@ void numgrad(NetView net, const double* X, const int* labels, int n, double reg,
 std::vector<double> train(NetView net, const double* X, const int* labels, int N, const TrainOpts& o) {
   const int P = net.P, H = net.H, C = net.C, B = o.batch;
   if (B <= 0) throw std::invalid_argument("batch size must be positive");
+  if (o.optim_kind >= 0 && (o.optim_kind > kAdam || !o.s1 || !o.counter || (o.optim_kind == kAdam && !o.s2)))
+    throw std::invalid_argument("train: a stateful optimizer needs its kind, state buffers and counter");
   std::vector<double> a1((size_t)B * H), yc((size_t)B * C);
   std::vector<double> dW1((size_t)H * P), db1(H), dW2((size_t)C * H), db2(C);
   std::vector<double> losses;
@@ -193,10 +195,30 @@ std::vector<double> train(NetView net, const double* X, const int* labels, int N
         std::printf("Loss at iteration %d of epoch %d/%d = %.10g\n", iter, epoch, o.epochs, l);
         std::fflush(stdout);
       }
-      for (int64_t i = 0; i < (int64_t)H * P; ++i) net.W1[i] -= o.lr * dW1[i];
-      for (int64_t i = 0; i < (int64_t)C * H; ++i) net.W2[i] -= o.lr * dW2[i];
-      for (int i = 0; i < H; ++i) net.b1[i] -= o.lr * db1[i];
-      for (int i = 0; i < C; ++i) net.b2[i] -= o.lr * db2[i];
+      if (o.optim_kind < 0) {
+        for (int64_t i = 0; i < (int64_t)H * P; ++i) net.W1[i] -= o.lr * dW1[i];
+        for (int64_t i = 0; i < (int64_t)C * H; ++i) net.W2[i] -= o.lr * dW2[i];
+        for (int i = 0; i < H; ++i) net.b1[i] -= o.lr * db1[i];
+        for (int i = 0; i < C; ++i) net.b2[i] -= o.lr * db2[i];
+      } else {
+        OptimHyper h = o.hyper;
+        h.lr = o.lr;
+        optim_advance(*o.counter, h);
+        double* prm[4] = {net.W1, net.b1, net.W2, net.b2};
+        const double* grd[4] = {dW1.data(), db1.data(), dW2.data(), db2.data()};
+        const int64_t cnt[4] = {(int64_t)H * P, H, (int64_t)C * H, C};
+        int64_t base = 0;
+        for (int q = 0; q < 4; base += cnt[q], ++q) {
+          if (o.optim_kind == kMomentum) {
+            const auto k = momentum_coef<double>(h);
+            for (int64_t i = 0; i < cnt[q]; ++i) momentum_update(prm[q][i], o.s1[base + i], grd[q][i], k);
+          } else {
+            const auto k = adam_coef<double>(h, *o.counter);
+            for (int64_t i = 0; i < cnt[q]; ++i)
+              adam_update(prm[q][i], o.s1[base + i], o.s2[base + i], grd[q][i], k);
+          }
+        }
+      }
       const bool print_flag = o.print_every <= 0 ? batch == 0 : iter % o.print_every == 0;
       if (o.debug && print_flag) {
         const std::string d = o.outdir + "/CPUmats/Sequential";

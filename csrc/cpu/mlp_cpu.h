@@ -14,6 +14,8 @@
 #include <string>
 #include <vector>
 
+#include "mlp/optim.h"
+
 namespace cme::cpu {
 
 struct NetView {
@@ -50,6 +52,15 @@ struct TrainOpts {
   std::string outdir = "Outputs";
   int ckpt_precision = 12;  // raw_ascii format, see io.h
   int iter0 = 0;            // iteration counter at the start (a resumed run continues the numbering)
+  // a stateful update rule (mlp/optim.h) instead of w -= lr g: optim_kind kMomentum / kAdam (-1: plain SGD, the
+  // fields below unused); hyper.lr is ignored (lr above is the rate); s1 (momentum: v; adam: m) and s2 (adam: s)
+  // hold H P + H + C H + C doubles in the order [W1|b1|W2|b2], and with counter are carried in and out, so
+  // one-epoch-at-a-time calls continue the state
+  int optim_kind = -1;
+  OptimHyper hyper{};
+  double* s1 = nullptr;
+  double* s2 = nullptr;
+  OptimCounter* counter = nullptr;
 };
 
 // Minibatch SGD (neural_network.cpp:219-279): ceil(N/B) batches per epoch, the
