@@ -58,6 +58,28 @@ class TrainConfig:
     beta1: float = 0.9          # --beta1
     beta2: float = 0.999        # --beta2
     adam_eps: float = 1e-8      # --adam-eps
+    lr_schedule: str = ""       # --lr-schedule constant | step | exp | linear | cosine (optim.Schedule); "": none
+    lr_gamma: float = 1.0       # --lr-gamma (step, exp)
+    lr_step_size: int = 1       # --lr-step-size (step)
+    lr_total: int = 1           # --lr-total (linear, cosine)
+    lr_end_factor: float = 1.0  # --lr-end-factor (linear)
+    lr_min_factor: float = 0.0  # --lr-min-factor (cosine)
+    lr_unit: str = "step"       # --lr-unit step | epoch
+    warmup: int = 0             # --warmup: linear warm-up over that many units (needs --lr-schedule)
+    warmup_start: float = 0.0   # --warmup-start: the factor of the first unit
+    clip_norm: float | None = None  # --clip-norm: clip the gradient's global norm (torch's clip_grad_norm_)
+
+    @property
+    def schedule(self):
+        """The optim.Schedule of the --lr-* flags, or None."""
+        from .optim import Schedule
+
+        if not self.lr_schedule:
+            return None
+        kind = {"exp": "exponential"}.get(self.lr_schedule, self.lr_schedule)
+        return Schedule(kind, unit=self.lr_unit, warmup=self.warmup, warmup_start=self.warmup_start,
+                        size=self.lr_step_size, gamma=self.lr_gamma, total=self.lr_total,
+                        end_factor=self.lr_end_factor, min_factor=self.lr_min_factor)
 
     @property
     def optim(self):
@@ -149,6 +171,21 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--beta1", type=float, help="Adam's first-moment decay (default 0.9)")
     ap.add_argument("--beta2", type=float, help="Adam's second-moment decay (default 0.999)")
     ap.add_argument("--adam-eps", type=float, help="Adam's epsilon (default 1e-8)")
+    ap.add_argument("--lr-schedule", choices=["constant", "step", "exp", "linear", "cosine"],
+                    help="learning-rate schedule: the rate of applied update t is -l times the schedule's factor "
+                         "(sequential and parallel run alike; the device reads the factors, so graphs replay across "
+                         "rates; --resume continues the sequence; data parallel only)")
+    ap.add_argument("--lr-gamma", type=float, help="decay factor in (0, 1] of step / exp (default 1)")
+    ap.add_argument("--lr-step-size", type=int, help="units between two decays of step (default 1)")
+    ap.add_argument("--lr-total", type=int, help="units over which linear / cosine run (default 1)")
+    ap.add_argument("--lr-end-factor", type=float, help="final factor of linear (default 1)")
+    ap.add_argument("--lr-min-factor", type=float, help="final factor of cosine (default 0)")
+    ap.add_argument("--lr-unit", choices=["step", "epoch"], help="what the schedule counts (default step)")
+    ap.add_argument("--warmup", type=int, help="linear warm-up over that many units before the schedule starts")
+    ap.add_argument("--warmup-start", type=float, help="the factor of the first warm-up unit (default 0)")
+    ap.add_argument("--clip-norm", type=float,
+                    help="clip the gradient's global L2 norm at this value before the update (torch's "
+                         "clip_grad_norm_, the regulariser included; formed on the device; data parallel only)")
     ap.add_argument("--gpus", type=int,
                     help="number of ranks, one per GPU (the reference's mpirun -np N); started here when no "
                          "launcher started this process")
@@ -181,8 +218,18 @@ def parse_config(argv=None) -> TrainConfig:
     # refused here, before any data is loaded or the sequential run starts: TensorParallelTrainer applies plain SGD only
     if cfg.parallel == "tp" and cfg.optimizer != "sgd":
         ap.error(f"--parallel tp applies plain SGD only; --optimizer {cfg.optimizer} needs --parallel dp")
+    if cfg.parallel == "tp" and (cfg.lr_schedule or cfg.clip_norm is not None):
+        ap.error("--parallel tp applies plain SGD at one rate only; --lr-schedule / --clip-norm need --parallel dp")
+    if not cfg.lr_schedule and any(k.startswith("lr_") or k.startswith("warmup") for k in explicit
+                                   if k != "lr_schedule"):
+        ap.error("--lr-gamma, --lr-step-size, --lr-total, --lr-end-factor, --lr-min-factor, --lr-unit, --warmup and "
+                 "--warmup-start need --lr-schedule")
     try:
         cfg.optim  # the hyper-parameters' ranges (optim.Optimizer validates)
+        cfg.schedule
+        from .optim import resolve_policy
+
+        resolve_policy(None, cfg.clip_norm)
     except ValueError as ex:
         ap.error(str(ex))
     return cfg

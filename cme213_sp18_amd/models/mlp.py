@@ -108,13 +108,22 @@ def numgrad(nn: NeuralNetwork, X, labels, reg: float, shift: bool = True) -> Gra
 def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, epochs: int = 15,
           batch_size: int = 800, grad_check: bool = False, print_every: int = -1, debug: bool = False,
           outdir: str = "Outputs", shift: bool = True, ckpt_precision: int = 12, iter0: int = 0,
-          shuffle_seed: int | None = None, optimizer=None, optim_state: dict | None = None) -> list[float]:
+          shuffle_seed: int | None = None, optimizer=None, optim_state: dict | None = None, schedule=None,
+          clip_norm: float | None = None, update_log: list | None = None) -> list[float]:
     """Sequential fp64 minibatch SGD on the CPU -- the oracle (neural_network.cpp:219-279).
 
     ``optimizer``: an ``optim.Optimizer`` (None or ``Optimizer.sgd()``: the reference's plain update).  A stateful
     rule (momentum, Adam; csrc/mlp/optim.h) keeps its state in ``optim_state`` -- ``optim.new_state(optimizer,
     nn.num_params())``, updated in place, so a later call (a resumed run, or one epoch at a time) continues it; None:
     a fresh state for this call.
+
+    ``schedule`` (an ``optim.Schedule``) and ``clip_norm``: the rate of applied update t is ``learning_rate *
+    schedule.factor(t, steps per epoch)`` -- the native loop takes the table of this call's rates -- and the gradient's
+    global norm is clipped at ``clip_norm`` in the one summation order of csrc/mlp/clip.h (torch's clip_grad_norm_ with
+    the L2 term in the loss).  With either set, plain SGD runs the stateless kSgd rule of csrc/mlp/optim.h and keeps its
+    update count in ``optim_state`` too (``optim.new_state(optimizer, n, policy=True)``: kind "sgd", no buffers).
+    ``update_log``: a list that receives one ``(t, rate, grad_norm, clip_coef)`` per update (norm NaN, coefficient 1
+    without clipping).
 
     ``iter0``: the iteration counter at the start -- a resumed run continues the loss / snapshot numbering.
 
@@ -137,32 +146,50 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
         ng = numgrad(nn, X[:n], labels[:n], reg, shift)
         if not gradcheck(ng, g):
             raise AssertionError("gradient check failed")
-    from ..optim import new_state, resolve
+    from ..optim import SGD_CODE, Optimizer, new_state, resolve, resolve_policy
 
     opt = resolve(optimizer)
+    schedule, clip = resolve_policy(schedule, clip_norm)
+    policy = schedule is not None or clip > 0.0
     kw = {}
-    if opt is not None:
-        st = optim_state if optim_state is not None else new_state(opt, nn.num_params())
-        if st["kind"] != opt.kind or any(s.size != nn.num_params() or s.dtype != np.float64 for s in st["state"]):
+    n, nb = X.shape[0], (X.shape[0] + int(batch_size) - 1) // int(batch_size)
+    rates = None
+    if opt is not None or policy:
+        st = optim_state if optim_state is not None else new_state(opt, nn.num_params(), policy=policy)
+        kind = opt.kind if opt is not None else "sgd"
+        if st["kind"] != kind or len(st["state"]) != (opt.num_state if opt is not None else 0) or any(
+                s.size != nn.num_params() or s.dtype != np.float64 for s in st["state"]):
             raise ValueError("optim_state does not belong to this optimizer and network")
         counter = np.array([st["t"], st["b1p"], st["b2p"]], np.float64)
-        kw["optim"] = (opt.code, opt.hyper(learning_rate), st["state"][0],
-                       st["state"][1] if opt.num_state > 1 else None, counter)
+        kw["optim"] = (opt.code if opt is not None else SGD_CODE,
+                       (opt if opt is not None else Optimizer.sgd()).hyper(learning_rate),
+                       st["state"][0] if st["state"] else None, st["state"][1] if len(st["state"]) > 1 else None,
+                       counter)
+        if policy:
+            kw["clip_norm"] = clip
+            kw["update_log"] = update_log
+        if schedule is not None:  # lr * factor: the fp64 product the apply launch forms
+            rates = float(learning_rate) * schedule.factors(int(st["t"]), int(epochs) * nb, nb)
+    elif update_log is not None:
+        raise ValueError("update_log needs a schedule, clip_norm or a stateful optimizer")
     try:
         if shuffle_seed is None:
+            if rates is not None:
+                kw["rates"] = rates
             return list(cpu().train(*nn.params, X, labels, float(learning_rate), float(reg), int(epochs),
                                     int(batch_size), int(print_every), bool(debug), outdir, shift,
                                     int(ckpt_precision), int(iter0), **kw))
         losses: list[float] = []
-        n = X.shape[0]
         it = int(iter0)
-        for _ in range(int(epochs)):
+        for ep in range(int(epochs)):
             perm = cpu().epoch_permutation(n, int(shuffle_seed), it)
+            if rates is not None:
+                kw["rates"] = np.ascontiguousarray(rates[ep * nb:(ep + 1) * nb])
             losses += cpu().train(*nn.params, np.ascontiguousarray(X[perm]), np.ascontiguousarray(labels[perm]),
                                   float(learning_rate), float(reg), 1, int(batch_size), int(print_every),
                                   bool(debug), outdir, shift, int(ckpt_precision), it, **kw)
-            it += (n + int(batch_size) - 1) // int(batch_size)
+            it += nb
         return losses
     finally:
-        if opt is not None:
+        if opt is not None or policy:
             st["t"], st["b1p"], st["b2p"] = int(counter[0]), float(counter[1]), float(counter[2])

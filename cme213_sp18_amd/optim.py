@@ -15,11 +15,135 @@
 from __future__ import annotations
 
 import dataclasses
+import math
 
 import numpy as np
 
 KINDS = ("sgd", "momentum", "adam")
 KIND_CODES = {"momentum": 0, "adam": 1}  # csrc/mlp/optim.h OptimKind
+SGD_CODE = 2  # kSgd: the stateless rule plain SGD runs through the apply launch under a schedule or clipping
+SCHEDULES = ("constant", "step", "exponential", "linear", "cosine")
+UNITS = ("step", "epoch")
+
+
+@dataclasses.dataclass(frozen=True)
+class Schedule:
+    """A learning-rate schedule: the rate of applied update ``t`` (0-based) is ``lr * factor(t, steps_per_epoch)``,
+    ``lr`` still the ``lr`` of ``train()`` / ``step()``.  Only the host evaluates the formulas (in fp64); the device
+    reads the factors from a window the trainer fills (csrc/mlp/optim.h).
+
+    With ``u = t`` (unit "step") or ``t // steps_per_epoch`` (unit "epoch") and ``v = u - warmup``:
+      * ``u < warmup``: ``warmup_start + (1 - warmup_start) * u / warmup``;
+      * constant ``1``; step ``gamma ** (v // size)``; exponential ``gamma ** v``;
+      * linear ``1 + (end_factor - 1) * min(v, total) / total``;
+      * cosine ``min_factor + (1 - min_factor) * (1 + cos(pi * min(v, total) / total)) / 2``.
+    """
+    kind: str = "constant"
+    unit: str = "step"
+    warmup: int = 0
+    warmup_start: float = 0.0
+    size: int = 1
+    gamma: float = 1.0
+    total: int = 1
+    end_factor: float = 1.0
+    min_factor: float = 0.0
+
+    def __post_init__(self):
+        if self.kind not in SCHEDULES:
+            raise ValueError(f"schedule kind must be one of {SCHEDULES}, got {self.kind!r}")
+        if self.unit not in UNITS:
+            raise ValueError(f"schedule unit must be one of {UNITS}, got {self.unit!r}")
+        for name in ("warmup", "size", "total"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError(f"{name} must be an integer, got {v!r}")
+        if int(self.warmup) < 0:
+            raise ValueError(f"warmup must be >= 0, got {self.warmup}")
+        if int(self.size) < 1:
+            raise ValueError(f"size must be >= 1, got {self.size}")
+        if int(self.total) < 1:
+            raise ValueError(f"total must be >= 1, got {self.total}")
+        if not 0.0 < float(self.gamma) <= 1.0:
+            raise ValueError(f"gamma must be in (0, 1], got {self.gamma}")
+        for name in ("warmup_start", "end_factor", "min_factor"):
+            if not float(getattr(self, name)) >= 0.0:
+                raise ValueError(f"{name} must be >= 0, got {getattr(self, name)}")
+
+    @staticmethod
+    def _common(unit, warmup, warmup_start) -> dict:
+        return dict(unit=unit, warmup=warmup, warmup_start=float(warmup_start))
+
+    @classmethod
+    def constant(cls, unit: str = "step", warmup: int = 0, warmup_start: float = 0.0) -> "Schedule":
+        return cls("constant", **cls._common(unit, warmup, warmup_start))
+
+    @classmethod
+    def step(cls, size: int, gamma: float, unit: str = "step", warmup: int = 0,
+             warmup_start: float = 0.0) -> "Schedule":
+        return cls("step", size=size, gamma=float(gamma), **cls._common(unit, warmup, warmup_start))
+
+    @classmethod
+    def exponential(cls, gamma: float, unit: str = "step", warmup: int = 0, warmup_start: float = 0.0) -> "Schedule":
+        return cls("exponential", gamma=float(gamma), **cls._common(unit, warmup, warmup_start))
+
+    @classmethod
+    def linear(cls, total: int, end_factor: float, unit: str = "step", warmup: int = 0,
+               warmup_start: float = 0.0) -> "Schedule":
+        return cls("linear", total=total, end_factor=float(end_factor), **cls._common(unit, warmup, warmup_start))
+
+    @classmethod
+    def cosine(cls, total: int, min_factor: float = 0.0, unit: str = "step", warmup: int = 0,
+               warmup_start: float = 0.0) -> "Schedule":
+        return cls("cosine", total=total, min_factor=float(min_factor), **cls._common(unit, warmup, warmup_start))
+
+    def factor(self, t: int, steps_per_epoch: int = 1) -> float:
+        t = int(t)
+        if t < 0:
+            raise ValueError("t is the 0-based index of an applied update")
+        if self.unit == "epoch":
+            if int(steps_per_epoch) < 1:
+                raise ValueError("steps_per_epoch must be >= 1")
+            u = t // int(steps_per_epoch)
+        else:
+            u = t
+        w = int(self.warmup)
+        if u < w:
+            return float(self.warmup_start + (1.0 - self.warmup_start) * u / w)
+        v = u - w
+        if self.kind == "constant":
+            return 1.0
+        if self.kind == "step":
+            return float(self.gamma ** (v // int(self.size)))
+        if self.kind == "exponential":
+            return float(self.gamma ** v)
+        total = int(self.total)
+        if self.kind == "linear":
+            return float(1.0 + (self.end_factor - 1.0) * min(v, total) / total)
+        return float(self.min_factor + (1.0 - self.min_factor) * (1.0 + math.cos(math.pi * min(v, total) / total)) / 2.0)
+
+    def factors(self, t0: int, n: int, steps_per_epoch: int = 1) -> np.ndarray:
+        """factor(t0 .. t0 + n) as a float64 array: one schedule window."""
+        return np.array([self.factor(int(t0) + i, steps_per_epoch) for i in range(int(n))], np.float64)
+
+    def key(self) -> tuple:
+        return dataclasses.astuple(self)
+
+    def as_meta(self) -> dict:
+        return dataclasses.asdict(self)
+
+    @classmethod
+    def from_meta(cls, d: dict | None) -> "Schedule | None":
+        return cls(**d) if d else None
+
+
+def resolve_policy(schedule, clip_norm) -> tuple:
+    """(schedule | None, clip_norm as a float, 0.0 = no clipping), validated."""
+    if schedule is not None and not isinstance(schedule, Schedule):
+        raise TypeError("schedule must be a Schedule or None")
+    c = 0.0 if clip_norm is None else float(clip_norm)
+    if clip_norm is not None and not (c > 0.0 and math.isfinite(c)):
+        raise ValueError(f"clip_norm must be a finite number > 0 (None: no clipping), got {clip_norm}")
+    return schedule, c
 
 
 @dataclasses.dataclass(frozen=True)
@@ -110,10 +234,13 @@ def resolve(opt) -> Optimizer | None:
     return opt if opt.stateful else None
 
 
-def new_state(opt: Optimizer | None, count: int) -> dict | None:
+def new_state(opt: Optimizer | None, count: int, policy: bool = False) -> dict | None:
     """A fresh host state for ``count`` parameters ([W1|b1|W2|b2], unpadded): fp64 buffers and the counter
-    {t, b1^t, b2^t} -- what ``models.mlp.train(optim_state=...)`` carries and ``MlpEngine.optim_state()`` returns."""
+    {t, b1^t, b2^t} -- what ``models.mlp.train(optim_state=...)`` carries and ``MlpEngine.optim_state()`` returns.
+    ``policy``: a schedule or clipping is set, so plain SGD keeps a counter too (kind "sgd", no buffers)."""
     opt = resolve(opt)
+    if opt is None and policy:
+        return {"kind": "sgd", "t": 0, "b1p": 1.0, "b2p": 1.0, "state": []}
     if opt is None:
         return None
     return {"kind": opt.kind, "t": 0, "b1p": 1.0, "b2p": 1.0,

@@ -170,6 +170,12 @@ class MlpEngine:
         # the update rule of apply() (set_optimizer): None = plain SGD, no state; else the state buffers and the
         # device-resident counter records of a stateful optimizer
         self.optimizer, self.opt_bufs, self.opt_rec = None, [], None
+        # the update policy of apply() (set_update_policy): a learning-rate schedule (optim.Schedule) and / or a
+        # gradient-norm threshold.  With either set, every update -- plain SGD's too, as the stateless kSgd rule -- goes
+        # through the apply launch: the schedule window {t0, n, f[0 .. n)} and its host copy, the sum-of-squares
+        # partials (csrc/mlp/clip.h) and the last-update record {t, lr_t, grad_norm, clip_coef}
+        self.schedule, self.clip_norm = None, 0.0
+        self.sched_win = self._win_host = self.clip_partials = self.opt_last = None
 
     def _configure_path(self):
         dev = self.device
@@ -655,19 +661,107 @@ class MlpEngine:
         from ..optim import resolve
 
         self.optimizer = resolve(opt)
-        if self.optimizer is None:
+        self._alloc_update_state()
+
+    def _alloc_update_state(self) -> None:
+        if not self.uses_apply_launch:
             self.opt_bufs, self.opt_rec = [], None
             return
         dev = self.device
         self.opt_bufs = [torch.zeros(self.layout.total, dtype=self.pdt, device=dev)
-                         for _ in range(self.optimizer.num_state)]
+                         for _ in range(self.optimizer.num_state if self.optimizer is not None else 0)]
         nrec = int(hip().optim_grid(self.layout.total)) if self.backend == "hip" else 1
         self.opt_rec = torch.zeros(nrec, 4, dtype=torch.float64, device=dev)
         self.reset_optimizer()
 
+    WINDOW_MIN_CAP = 256  # factors the schedule window holds before it has to grow
+
+    @property
+    def policy_set(self) -> bool:
+        return self.schedule is not None or self.clip_norm > 0.0
+
+    @property
+    def uses_apply_launch(self) -> bool:
+        """apply() is the one launch of csrc/mlp/optim.hip (a stateful rule, or plain SGD under a schedule or
+        clipping) rather than sgd(lr)."""
+        return self.optimizer is not None or self.policy_set
+
+    def set_update_policy(self, schedule=None, clip_norm=None) -> None:
+        """A learning-rate schedule (optim.Schedule) and / or gradient-norm clipping at ``clip_norm`` for apply().
+        With neither, nothing changes and nothing is allocated.  With either, plain SGD becomes the stateless kSgd rule
+        through the apply launch (counter records allocated, update count reset to 0); a stateful optimizer keeps its
+        state.  The clipped gradient is the one the step leaves -- scaled, regulariser included: torch's
+        clip_grad_norm_ with the L2 term in the loss; a non-finite norm propagates as torch's default does.  The window
+        starts as the single factor of update 0: set_schedule_window() (DataParallelTrainer does) fills it."""
+        from ..optim import resolve_policy
+
+        had = self.uses_apply_launch
+        self.schedule, self.clip_norm = resolve_policy(schedule, clip_norm)
+        dev = self.device
+        if not self.policy_set:
+            self.sched_win = self._win_host = self.clip_partials = self.opt_last = None
+            if had and self.optimizer is None:
+                self._alloc_update_state()
+            return
+        if not had:
+            self._alloc_update_state()
+        self.opt_last = torch.tensor([-1.0, float("nan"), float("nan"), 1.0], dtype=torch.float64, device=dev)
+        self.clip_partials = None
+        if self.clip_norm > 0.0:
+            self.clip_partials = torch.zeros(64, dtype=torch.float64, device=dev)  # (clip.h kClipMaxGrid)
+        self.sched_win = self._win_host = None
+        if self.schedule is not None:
+            self.sched_win = torch.zeros(2 + self.WINDOW_MIN_CAP, dtype=torch.float64, device=dev)
+            self.set_schedule_window(0, self.schedule.factors(0, 1))
+
+    def clip_segments(self) -> list:
+        """The (offset, size) pairs of [W1|b1|W2|b2] in the arena: what enters the gradient norm (never a segment's
+        padding, never the status element)."""
+        return [(int(o), int(s)) for o, s in zip(self.layout.offsets[:4], self.layout.sizes[:4])]
+
+    def set_schedule_window(self, t0: int, factors) -> bool:
+        """Fill the schedule window: update t0 + i gets factors[i]; an update outside [t0, t0 + n) takes the nearest
+        end's factor.  A copy into the resident buffer, in place -- captured graphs stay valid -- unless the factors
+        outgrow its capacity: then the buffer is reallocated and True is returned (graphs captured against the old one
+        must be dropped).  Never call it during a capture."""
+        if self.schedule is None:
+            raise RuntimeError("set_update_policy() with a schedule first")
+        f = np.ascontiguousarray(factors, dtype=np.float64).reshape(-1)
+        t0, n = int(t0), int(f.size)
+        if t0 < 0 or n < 1:
+            raise ValueError("a schedule window needs t0 >= 0 and at least one factor")
+        if not bool(np.all(f >= 0.0)):
+            raise ValueError("schedule factors must be >= 0")
+        grew = False
+        if n > self.sched_win.numel() - 2:
+            cap = max(n, 2 * (self.sched_win.numel() - 2))
+            self.sched_win = torch.zeros(2 + cap, dtype=torch.float64, device=self.device)
+            grew = True
+        host = np.concatenate([[float(t0), float(n)], f])
+        with torch.no_grad():
+            self.sched_win[:host.size].copy_(torch.from_numpy(host))
+        self._win_host = (t0, f.copy())
+        return grew
+
+    def update_count(self) -> int:
+        """The count of applied updates (the device-resident record).  Synchronises."""
+        if self.opt_rec is None:
+            raise RuntimeError("plain SGD without a schedule or clipping keeps no update count")
+        return int(self.opt_rec[0, 0].item())
+
+    def last_update(self) -> dict | None:
+        """{t, lr, grad_norm, clip_coef} of the last applied update under a schedule or clipping (grad_norm None
+        without clipping; None before the first update).  Synchronises."""
+        if self.opt_last is None:
+            raise RuntimeError("set_update_policy() first")
+        t, lr, norm, coef = self.opt_last.cpu().tolist()
+        if t < 0:
+            return None
+        return {"t": int(t), "lr": lr, "grad_norm": None if self.clip_norm <= 0.0 else norm, "clip_coef": coef}
+
     def reset_optimizer(self) -> None:
         """Zero the optimizer state and the update count."""
-        if self.optimizer is None:
+        if self.opt_rec is None:
             return
         with torch.no_grad():
             for b in self.opt_bufs:
@@ -681,19 +775,23 @@ class MlpEngine:
         """Host copy of the optimizer state: {kind, t, b1p, b2p, state: [fp64 arrays over [W1|b1|W2|b2], unpadded]}
         (the layout of optim.new_state and models.mlp.train); None for plain SGD.  Checks that every workgroup's
         counter record agrees.  Synchronises."""
-        if self.optimizer is None:
+        if self.opt_rec is None:
             return None
         rec = self.opt_rec.cpu()
         if not bool((rec == rec[0]).all()):
             raise RuntimeError("optimizer counter records disagree: " + str(rec[:, :3].unique(dim=0).tolist()))
-        return {"kind": self.optimizer.kind, "t": int(rec[0, 0]), "b1p": float(rec[0, 1]), "b2p": float(rec[0, 2]),
+        return {"kind": self._rule_kind, "t": int(rec[0, 0]), "b1p": float(rec[0, 1]), "b2p": float(rec[0, 2]),
                 "state": [self._unpadded(b) for b in self.opt_bufs]}
 
+    @property
+    def _rule_kind(self) -> str:
+        return self.optimizer.kind if self.optimizer is not None else "sgd"
+
     def set_optim_state(self, st: dict) -> None:
-        if self.optimizer is None:
-            raise RuntimeError("set_optimizer() with a stateful optimizer first")
-        if st["kind"] != self.optimizer.kind or len(st["state"]) != len(self.opt_bufs):
-            raise ValueError(f"the state is a {st['kind']} state, the optimizer is {self.optimizer.kind}")
+        if self.opt_rec is None:
+            raise RuntimeError("set_optimizer() with a stateful optimizer (or set_update_policy()) first")
+        if st["kind"] != self._rule_kind or len(st["state"]) != len(self.opt_bufs):
+            raise ValueError(f"the state is a {st['kind']} state, the optimizer is {self._rule_kind}")
         srcs = [torch.as_tensor(np.asarray(s, np.float64)).reshape(-1) for s in st["state"]]
         count = sum(v.numel() for v in self.layout.views(self.params))
         if any(s.numel() != count for s in srcs):  # (before anything is copied)
@@ -713,8 +811,11 @@ class MlpEngine:
         launch of the stateful kernel (csrc/mlp/optim.hip), which also refreshes the bf16 planes / shadow of W1,
         advances the device-resident update count and applies nothing when the bucket's status element is non-zero.
         No host sync: legal under stream capture."""
-        if self.optimizer is None:
+        if not self.uses_apply_launch:
             self.sgd(lr)
+            return
+        if self.policy_set:
+            self._apply_policy(lr)
             return
         o = self.optimizer
         self._w1_written()
@@ -741,6 +842,64 @@ class MlpEngine:
                     if dst is not None:
                         dst.copy_(src)
             self.opt_rec.copy_(torch.tensor([float(t), b1p, b2p, 0.0], dtype=torch.float64).expand_as(self.opt_rec))
+            self.refresh_shadow()
+
+    def _apply_policy(self, lr: float) -> None:
+        """apply() under a schedule and / or clipping: (clipping) the sum-of-squares launch over the four parameter
+        segments, then the ONE apply launch, which combines the partials, reads the update's factor from the window and
+        leaves the last-update record.  The torch backend evaluates the same header on the host (_cpu.grad_clip,
+        _cpu.window_rate, _cpu.optim_step)."""
+        from ..optim import SGD_CODE, Optimizer
+
+        o = self.optimizer
+        code = o.code if o is not None else SGD_CODE
+        hyper = (o if o is not None else Optimizer.sgd()).hyper
+        self._w1_written()
+        if self.backend == "hip":
+            m = hip()
+            st = torch.cuda.current_stream(self.device).cuda_stream
+            dt = 0 if self.pdt == torch.float32 else 1
+            npart = 0
+            if self.clip_norm > 0.0:
+                segs = self.clip_segments()
+                npart = int(m.clip_grid(sum(s for _, s in segs)))
+                m.grad_sumsq(dt, self.grads.data_ptr(), self.layout.total, segs, self.clip_partials.data_ptr(), npart,
+                             st)
+            planes, np_ = (self.W1p, self.np) if self.np else ((self.W1g, 1) if self.dtype == "bf16" else (None, 0))
+            win = self.sched_win
+            m.optim_apply(dt, code, *hyper(lr), self.params.data_ptr(), self.grads.data_ptr(),
+                          self.opt_bufs[0].data_ptr() if self.opt_bufs else 0,
+                          self.opt_bufs[1].data_ptr() if len(self.opt_bufs) > 1 else 0, self.layout.total,
+                          planes.data_ptr() if planes is not None else 0, np_, self.H * self.P if np_ else 0,
+                          self.grads[self.status_index:].data_ptr(), self.opt_rec.data_ptr(),
+                          int(self.opt_rec.shape[0]), win.data_ptr() if win is not None else 0,
+                          int(win.numel()) - 2 if win is not None else 0,
+                          self.clip_partials.data_ptr() if npart else 0, npart, self.clip_norm,
+                          self.opt_last.data_ptr(), st)
+            return
+        with torch.no_grad():
+            if float(self.grads[self.status_index]) != 0.0:
+                return
+            host = self.device.type == "cpu"
+            arrs = [t if host else t.cpu() for t in (self.params, self.grads, *self.opt_bufs)]
+            g = arrs[1].numpy().copy()  # (the bucket itself stays as the step left it, as on the device)
+            rec = self.opt_rec[0].cpu()
+            t = int(rec[0])
+            lr_t = float(lr)
+            if self._win_host is not None:
+                lr_t = float(cpu().window_rate(float(lr), float(self._win_host[0]), self._win_host[1], t))
+            norm, coef = float("nan"), 1.0
+            if self.clip_norm > 0.0:
+                norm, coef = cpu().grad_clip(g, self.clip_segments(), self.clip_norm)
+            state = [a.numpy() for a in arrs[2:]]
+            t1, b1p, b2p = cpu().optim_step(code, hyper(lr_t), arrs[0].numpy(), g, state[0] if state else None,
+                                            state[1] if len(state) > 1 else None, t, float(rec[1]), float(rec[2]))
+            if not host:
+                self.params.copy_(arrs[0])
+                for dst, src in zip(self.opt_bufs, arrs[2:]):
+                    dst.copy_(src)
+            self.opt_rec.copy_(torch.tensor([float(t1), b1p, b2p, 0.0], dtype=torch.float64).expand_as(self.opt_rec))
+            self.opt_last.copy_(torch.tensor([float(t), lr_t, norm, coef], dtype=torch.float64))
             self.refresh_shadow()
 
     def reg_only_grads(self, reg: float):

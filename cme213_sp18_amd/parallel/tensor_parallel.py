@@ -45,7 +45,8 @@ class TensorParallelTrainer:
 
     def __init__(self, nn, comm: Communicator | None = None, device=None, dtype: str = "f32",
                  batch_size: int = 800, backend: str = "hip", shift: bool = True, normalize: bool = False,
-                 path: str = "auto", allreduce: str = "auto", shuffle_seed: int | None = None, optimizer=None):
+                 path: str = "auto", allreduce: str = "auto", shuffle_seed: int | None = None, optimizer=None,
+                 schedule=None, clip_norm=None):
         from ..optim import resolve
 
         # the shard's update stays inside its weight-gradient launch (plain SGD); the stateful rules are
@@ -53,6 +54,9 @@ class TensorParallelTrainer:
         if resolve(optimizer) is not None:
             raise ValueError(f"tensor parallelism applies plain SGD only (got optimizer {optimizer.kind!r}); "
                              "use data parallelism (--parallel dp) for momentum or Adam")
+        if schedule is not None or clip_norm is not None:
+            raise ValueError("tensor parallelism applies plain SGD at one rate only: a learning-rate schedule or "
+                             "gradient-norm clipping needs data parallelism (--parallel dp)")
         self.nn = nn
         self.shuffle_seed = None if shuffle_seed is None else int(shuffle_seed)  # (DataParallelTrainer's)
         self.comm = comm or NullComm()

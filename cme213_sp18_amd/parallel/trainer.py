@@ -236,7 +236,7 @@ class DataParallelTrainer:
                  normalize: bool = False, path: str = "auto", allreduce: str = "auto", overlap: bool = True,
                  overlap_chunks: int = 0, fuse_allreduce: bool = True, executor: str = "auto",
                  grad_wire: str = "auto", fused_form: str = "auto", shuffle_seed: int | None = None,
-                 optimizer=None):
+                 optimizer=None, schedule=None, clip_norm=None):
         self.nn = nn
         # the update rule (optim.Optimizer): None / Optimizer.sgd() = the plain-SGD code as it stands.  A stateful
         # rule (momentum, Adam) runs every step in gradient mode followed by engine.apply() -- one extra launch --
@@ -245,6 +245,18 @@ class DataParallelTrainer:
         from ..optim import resolve
 
         self.optimizer = resolve(optimizer)
+        # a learning-rate schedule (optim.Schedule: the rate of applied update t is lr * factor(t)) and / or
+        # gradient-norm clipping at clip_norm (torch's clip_grad_norm_ on the gradient the step leaves, regulariser
+        # included; after the all-reduce, so every rank forms the same coefficient).  Either one sends every update
+        # -- plain SGD's too, as the stateless kSgd rule -- through gradient mode + the apply launch, like a stateful
+        # rule; the device reads the factor from a window train() / step() fill, so graphs replay across rates
+        from ..optim import resolve_policy
+
+        self.schedule, clip = resolve_policy(schedule, clip_norm)
+        self.clip_norm = clip if clip > 0.0 else None
+        self._policy = self.schedule is not None or self.clip_norm is not None
+        self._apply_launch = self.optimizer is not None or self._policy
+        self._win_left = 0  # updates the schedule window still covers on the hand-driven step() path
         self.native_reason = ""  # why native_plan() last returned None for a reason of the optimizer's
         # per-epoch shuffle of the resident training set (None: the loaded order every epoch, nothing kept or
         # launched): load() keeps the pristine rows and train() reorders every layout on the device before each
@@ -288,6 +300,7 @@ class DataParallelTrainer:
                                 path=path)
         self.engine.set_params(*nn.params)
         self.engine.set_optimizer(self.optimizer)
+        self.engine.set_update_policy(self.schedule, self.clip_norm)
         # training reads nothing of a1 after a step: the wide fused forward + head launch skips its 13 MB store
         # at H = 4096 (bench/wide_ag_ab.py: -1.4 us/step fp32, -2.1 us bf16)
         self.engine.set_store_a1(False)
@@ -315,7 +328,7 @@ class DataParallelTrainer:
         self._xgmi_fused = None
         self.fused_allreduce = False
         if (self.xgmi is not None and fuse_allreduce and self.xgmi.wire == self.engine.params.dtype
-                and self.xgmi.shots == 1 and self.optimizer is None):
+                and self.xgmi.shots == 1 and not self._apply_launch):
             slots = self.engine.fused_allreduce_slots()
             if self.fused_form == "auto":
                 self.fused_form = "pull"
@@ -460,7 +473,7 @@ class DataParallelTrainer:
         as_words = lambda t: t.view(torch.int32) if t.element_size() == 4 else t.view(torch.int16) \
             if t.element_size() == 2 else t.view(torch.int64)  # noqa: E731
         w = as_words(p).to(torch.int64)
-        if e.optimizer is not None:  # ... and the same optimizer state and update count
+        if e.opt_rec is not None:  # ... and the same optimizer state and update count
             w = torch.cat([w] + [as_words(b.detach().reshape(-1)).to(torch.int64) for b in e.opt_bufs]
                           + [e.opt_rec[0].view(torch.int64)])
         idx = torch.arange(1, w.numel() + 1, device=w.device, dtype=torch.int64)
@@ -518,7 +531,7 @@ class DataParallelTrainer:
             self.comm.allreduce_(e.grads)
             e.apply(lr)
             return
-        if self.optimizer is not None:  # the separate xGMI all-reduce, then the stateful launch
+        if self._apply_launch:  # the separate xGMI all-reduce, then the apply launch
             self.xgmi.allreduce_(e.grads)
             e.apply(lr)
             return
@@ -650,6 +663,8 @@ class DataParallelTrainer:
         the resident set: after a shuffled train() that is the last epoch's order (engine.permutation())."""
         e = self.engine
         off, n = self.shard(start, length)
+        if self.schedule is not None:
+            self._window_for_step()
         if self.profiler is not None and n > 0:
             self._profiled_step(off, n, 1.0 / (n * self.R), reg, lr, with_loss)
             return
@@ -658,7 +673,7 @@ class DataParallelTrainer:
             self._allreduce_sgd(lr)
             return
         scale = 1.0 / (n * self.R)
-        if self.optimizer is not None and isinstance(self.comm, NullComm) and self.allreduce_mode != "host":
+        if self._apply_launch and isinstance(self.comm, NullComm) and self.allreduce_mode != "host":
             e.run(off, n, scale, reg, lr, sgd=False, with_loss=with_loss)  # 1 process: gradient mode + apply
             e.apply(lr)
         elif isinstance(self.comm, NullComm) and self.allreduce_mode != "host":  # 1 process: SGD fused into wgrad
@@ -674,7 +689,7 @@ class DataParallelTrainer:
     def _profiled_step(self, off, n, scale, reg, lr, with_loss):
         """The same step, split into timed phases (PhaseTimer events + roctx ranges; eager only)."""
         e, P = self.engine, self.profiler
-        single = isinstance(self.comm, NullComm) and self.allreduce_mode != "host" and self.optimizer is None
+        single = isinstance(self.comm, NullComm) and self.allreduce_mode != "host" and not self._apply_launch
         if e.backend != "hip":
             with P.phase("step"):
                 if single:
@@ -767,7 +782,7 @@ class DataParallelTrainer:
         e.join()
         snap = (e.params.clone(), (e.W1g.clone() if e.W1g is not e.W1 else None),
                 (e.W1p.clone() if e.W1p is not None else None))
-        if e.optimizer is not None:  # the state buffers and every workgroup's counter record
+        if e.opt_rec is not None:  # the state buffers and every workgroup's counter record
             snap += ([b.clone() for b in e.opt_bufs], e.opt_rec.clone())
         return snap
 
@@ -787,7 +802,9 @@ class DataParallelTrainer:
     def capture(self, plan: EpochPlan, lr: float, reg: float) -> torch.cuda.CUDAGraph:
         """Capture every step of ``plan`` into one HIP graph (state-neutral warm-up first)."""
         key = (tuple(plan.steps), float(lr), float(reg)) + (
-            (self.optimizer.key(),) if self.optimizer is not None else ())
+            (self.optimizer.key(),) if self.optimizer is not None else ()) + (
+            (("schedule",) + self.schedule.key(),) if self.schedule is not None else ()) + (
+            (("clip", float(self.clip_norm)),) if self.clip_norm is not None else ())
         g = self._graphs.get(key)
         if g is not None:
             return g
@@ -815,6 +832,14 @@ class DataParallelTrainer:
         if self.optimizer is not None:
             self.native_reason = (f"stateful optimizer ({self.optimizer.kind}): every step runs in gradient mode "
                                   "followed by the optimizer launch")
+            if e.backend == "hip":
+                e._hip_step().xstep_reason = self.native_reason
+            return None
+        if self._policy:
+            what = " and ".join(w for w, on in (("a learning-rate schedule", self.schedule is not None),
+                                                ("gradient-norm clipping", self.clip_norm is not None)) if on)
+            self.native_reason = (f"{what}: every step runs in gradient mode followed by the apply launch, which "
+                                  "reads the update's rate and the gradient norm on the device")
             if e.backend == "hip":
                 e._hip_step().xstep_reason = self.native_reason
             return None
@@ -867,6 +892,31 @@ class DataParallelTrainer:
             self.engine.mark_planes_stale()  # (the replay's in-place updates skipped the plane refresh)
         else:
             self._enqueue_plan(plan, lr, reg)
+
+    # ------------------------------------------------------------- schedule window
+    def steps_per_epoch(self) -> int:
+        return len(self.epoch_plan().steps)
+
+    def _fill_window(self, updates: int) -> None:
+        """The schedule window for the next ``updates`` applied updates, from the device's update count (read once:
+        synchronises).  A refill in place; a window that outgrew its buffer drops the captured graphs."""
+        e = self.engine
+        t0 = e.update_count()
+        if e.set_schedule_window(t0, self.schedule.factors(t0, max(1, int(updates)), self.steps_per_epoch())):
+            self._graphs.clear()
+
+    def _window_for_step(self) -> None:
+        """step() outside train(): the hand-driven loop gets the same rates.  The window is refilled (a sync: this is
+        the eager path) whenever the host has enqueued as many updates as it covers; never during a capture."""
+        if self._win_left > 0:
+            self._win_left -= 1
+            return
+        e = self.engine
+        if e.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            return
+        n = max(1, self.steps_per_epoch() if hasattr(self, "N") else 1)
+        self._fill_window(n)
+        self._win_left = n - 1
 
     # ------------------------------------------------------------- recovery
     def _fall_back_to_comm(self) -> None:
@@ -948,6 +998,13 @@ class DataParallelTrainer:
         forms the same order from the same seed.  The validation set is never shuffled.  Afterwards the set stays in
         the last epoch's order.
 
+        With a schedule (the constructor's), the call reads the device's update count once, behind its start-of-call
+        sync, and fills the schedule window for ``epochs * steps_per_epoch`` updates from there, steps_per_epoch =
+        len(epoch_plan().steps): the apply launch looks its factor up on the device, so every epoch replays from the
+        same graph, train(2) + train(2) equals train(4), a recovered epoch (count restored) gets the same rates again
+        and a resumed run (count restored by set_optim_state) continues the sequence.  When the host looks at a step
+        anyway (print_every), the loss event gains ``lr`` and ``grad_norm`` (engine.last_update()).
+
         With the xGMI all-reduce, every epoch ends with a collective check of the peer-wait error flag
         (assert_comm_ok): a timed-out wait raises CommFailure on every rank before another epoch runs."""
         from ..utils.checkpoint import write_diff_gpu_cpu
@@ -992,6 +1049,9 @@ class DataParallelTrainer:
         dev = self.engine.device
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
+        if self.schedule is not None:  # behind the sync: the device's update count, read once
+            self._fill_window(epochs * len(plan.steps))
+            self._win_left = 1 << 62  # (step() inside this call leaves the window alone)
         self.comm.barrier()
         t0 = time.perf_counter()
         def maybe_fault(first: int, count: int):
@@ -1030,8 +1090,17 @@ class DataParallelTrainer:
                     stats.losses.append(l)
                     if self.rank == 0:
                         log(f"Loss at iteration {it} of epoch {epoch}/{epochs} = {l:.10g}")
+                    upd = self.engine.last_update() if self._policy else None
+                    if upd is not None and self.rank == 0:
+                        norm = upd["grad_norm"]
+                        log(f"  update {upd['t']}: lr = {upd['lr']:.10g}"
+                            + (f", grad norm = {norm:.10g} (coefficient {upd['clip_coef']:.6g})"
+                               if norm is not None else ""))
                     if on_event is not None:
-                        on_event({"event": "loss", "iter": it, "epoch": epoch, "loss": l})
+                        ev = {"event": "loss", "iter": it, "epoch": epoch, "loss": l}
+                        if upd is not None:
+                            ev.update(lr=upd["lr"], grad_norm=upd["grad_norm"])
+                        on_event(ev)
                 else:
                     self.step(s, ln, lr, reg)
                 print_flag = (bi == 0) if print_every <= 0 else (it % print_every == 0)
@@ -1079,6 +1148,7 @@ class DataParallelTrainer:
                 stats.evals = [{"epoch": ev_meta[s_][0], "iter": ev_meta[s_][1], **ev_read[s_]} for s_ in range(n_ev)]
             self.comm.barrier()
         finally:
+            self._win_left = 0  # (a hand-driven step() after this call refills the window from the device's count)
             if own_file:
                 err_file.close()
         stats.seconds = time.perf_counter() - t0

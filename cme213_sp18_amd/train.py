@@ -100,14 +100,23 @@ def run(cfg: TrainConfig) -> dict:
         os.makedirs(cfg.outdir, exist_ok=True)
         meta = {}
         opt = cfg.optim
+        sched, clip = cfg.schedule, cfg.clip_norm
+        policy = sched is not None or clip is not None  # (plain SGD then keeps an update count too: optim_t)
+        keeps_state = opt.stateful or policy
         opt_state = None  # the checkpoint's optimizer state (both runs continue it)
         if cfg.resume:
             nn, meta = load_checkpoint(cfg.resume)
             log0(rank, f"Resumed from {cfg.resume}: {meta}")
             saved = Optimizer.from_meta(meta.get("optimizer"))  # (no record: plain SGD)
             same = saved == opt if opt.stateful else not saved.stateful
-            if opt.stateful and same:
+            if keeps_state and same:
                 opt_state = load_optim_state(cfg.resume, meta)
+            from .optim import Schedule
+
+            if Schedule.from_meta(meta.get("schedule")) != sched or meta.get("clip_norm") != clip:
+                log0(rank, f"warning: the checkpoint was trained with schedule {meta.get('schedule')} and clip norm "
+                           f"{meta.get('clip_norm')}, this run uses {sched.as_meta() if sched else None} and {clip}: "
+                           "the rates do not continue the checkpoint's")
             if not same:
                 log0(rank, f"warning: the checkpoint was trained with optimizer {saved}, this run uses {opt}: the "
                            "optimizer state starts fresh")
@@ -128,7 +137,7 @@ def run(cfg: TrainConfig) -> dict:
             mlp.train(seq_nn, xs, ds.y_train, cfg.learning_rate, cfg.reg, cfg.num_epochs, cfg.batch_size,
                       False, cfg.print_every, cfg.debug, cfg.outdir, cfg.softmax_shift, cfg.ckpt_precision,
                       iter0=int(meta.get("iter", 0)), shuffle_seed=cfg.shuffle_seed, optimizer=opt,
-                      optim_state=copy.deepcopy(opt_state))
+                      optim_state=copy.deepcopy(opt_state), schedule=sched, clip_norm=clip)
             out["seq_seconds"] = time.perf_counter() - t
             log0(rank, f"Time for Sequential Training: {out['seq_seconds']:.6f} seconds")
             out["seq_dev_precision"] = precision(mlp.predict(seq_nn, xd, cfg.softmax_shift), ds.y_dev)
@@ -145,13 +154,14 @@ def run(cfg: TrainConfig) -> dict:
                                        backend=backend, shift=cfg.softmax_shift, normalize=cfg.normalize,
                                        path=cfg.path,
                                        allreduce=tp_allreduce_mode(cfg.allreduce), shuffle_seed=cfg.shuffle_seed,
-                                       optimizer=opt)
+                                       optimizer=opt, schedule=sched, clip_norm=clip)
             tr.use_graphs = cfg.use_graphs
         else:
             tr = DataParallelTrainer(nn, comm=comm, device=device, dtype=cfg.dtype, batch_size=cfg.batch_size,
                                      backend=backend, shift=cfg.softmax_shift, use_graphs=cfg.use_graphs,
                                      normalize=cfg.normalize, path=cfg.path, allreduce=cfg.allreduce,
-                                     overlap_chunks=cfg.overlap_chunks, shuffle_seed=cfg.shuffle_seed, optimizer=opt)
+                                     overlap_chunks=cfg.overlap_chunks, shuffle_seed=cfg.shuffle_seed, optimizer=opt,
+                                     schedule=sched, clip_norm=clip)
             if opt_state is not None:
                 tr.engine.set_optim_state(opt_state)
         tr.load(ds.x_train, ds.y_train)
@@ -170,8 +180,10 @@ def run(cfg: TrainConfig) -> dict:
         ckpt_meta = lambda done: {"epochs": done + meta.get("epochs", 0), "lr": cfg.learning_rate, "reg": cfg.reg,
                                   "seed": cfg.seed, "dtype": cfg.dtype, "iter": tr.iter,
                                   "shuffle_seed": cfg.shuffle_seed,
-                                  **({"optimizer": opt.as_meta()} if opt.stateful else {})}
-        ckpt_optim = lambda: tr.engine.optim_state() if opt.stateful else None  # noqa: E731
+                                  **({"optimizer": opt.as_meta()} if opt.stateful else {}),
+                                  **({"schedule": sched.as_meta()} if sched is not None else {}),
+                                  **({"clip_norm": clip} if clip is not None else {})}
+        ckpt_optim = lambda: tr.engine.optim_state() if keeps_state else None  # noqa: E731
         seg = cfg.ckpt_every if (cfg.ckpt_every > 0 and cfg.ckpt_dir) else cfg.num_epochs
         done, st = 0, None
         while done < cfg.num_epochs or st is None:  # train in checkpoint segments

@@ -10,6 +10,7 @@
 #include "cpu/io.h"
 #include "cpu/mlp_cpu.h"
 #include "cpu/suite_cpu.h"
+#include "mlp/clip.h"
 #include "mlp/shuffle.h"
 
 namespace py = pybind11;
@@ -40,6 +41,35 @@ cme::OptimHyper hyper_of(py::handle h) {
   o.lr = t[0].cast<double>(); o.mu = t[1].cast<double>(); o.nesterov = t[2].cast<bool>() ? 1 : 0;
   o.beta1 = t[3].cast<double>(); o.beta2 = t[4].cast<double>(); o.eps = t[5].cast<double>();
   return o;
+}
+
+// [(offset, size), ...] -> the segments of clip.h, each inside an array of `len` elements
+cme::ClipSegs segs_of(const std::vector<std::pair<int64_t, int64_t>>& segments, int64_t len) {
+  if (segments.empty() || segments.size() > cme::kClipMaxSegs)
+    throw std::invalid_argument("1 .. 4 (offset, size) segments expected");
+  cme::ClipSegs s;
+  s.n = (int)segments.size();
+  for (int i = 0; i < s.n; ++i) {
+    s.off[i] = segments[i].first;
+    s.size[i] = segments[i].second;
+    if (s.off[i] < 0 || s.size[i] < 0 || s.off[i] > len || s.size[i] > len - s.off[i])
+      throw std::invalid_argument("a segment lies outside the array");
+  }
+  return s;
+}
+
+// the sum of squares of a float32 / float64 array's segments in clip.h's order: (partials, sumsq)
+std::pair<py::array_t<double>, double> sumsq_of(const py::array& g, const cme::ClipSegs& s) {
+  if (!(g.flags() & py::array::c_style)) throw std::invalid_argument("a C-contiguous array expected");
+  py::array_t<double> partials(cme::clip_grid(s.count()));
+  double total;
+  if (g.dtype().is(py::dtype::of<float>()))
+    total = cme::clip_host_sumsq(static_cast<const float*>(g.data()), s, partials.mutable_data());
+  else if (g.dtype().is(py::dtype::of<double>()))
+    total = cme::clip_host_sumsq(static_cast<const double*>(g.data()), s, partials.mutable_data());
+  else
+    throw std::invalid_argument("float32 or float64 array expected");
+  return {partials, total};
 }
 
 void check_x(const f64arr& X, int P) {
@@ -128,14 +158,18 @@ PYBIND11_MODULE(_cpu, m) {
       "train",
       [](py::array_t<double> W1, py::array_t<double> b1, py::array_t<double> W2, py::array_t<double> b2, f64arr X,
          i32arr labels, double lr, double reg, int epochs, int batch, int print_every, bool debug,
-         std::string outdir, bool shift, int ckpt_precision, int iter0, py::object optim) {
+         std::string outdir, bool shift, int ckpt_precision, int iter0, py::object optim, py::object rates,
+         double clip_norm, py::object update_log) {
         auto v = view(W1, b1, W2, b2);
         check_x(X, v.P);
         cme::cpu::TrainOpts o;
         o.lr = lr; o.reg = reg; o.epochs = epochs; o.batch = batch; o.print_every = print_every;
         o.debug = debug; o.outdir = outdir; o.shift = shift; o.ckpt_precision = ckpt_precision; o.iter0 = iter0;
         // optim: None, or (kind, hyper, s1, s2 | None, counter): the state arrays (float64, H P + H + C H + C) and
-        // the counter array {t, b1^t, b2^t} are updated in place
+        // the counter array {t, b1^t, b2^t} are updated in place; kind 2 (plain SGD under a schedule or clipping: the
+        // kSgd rule) has no state, s1 = s2 = None
+        // rates: None or the float64 rate of every update of the call; clip_norm: 0 = no clipping; update_log: None
+        // or a list that gets one (t, rate, grad_norm, clip_coef) per update
         cme::OptimCounter ctr;
         py::array_t<double> counter;
         if (!optim.is_none()) {
@@ -150,7 +184,8 @@ PYBIND11_MODULE(_cpu, m) {
             if (a.size() != total) throw std::invalid_argument("train: optimizer state must hold every parameter");
             return mut(a);
           };
-          o.s1 = state(t[2]);
+          if (o.optim_kind == cme::kSgd) o.optim_kind = -1;
+          else o.s1 = state(t[2]);
           if (!t[3].is_none()) o.s2 = state(t[3]);
           if (!py::isinstance<py::array_t<double>>(t[4])) throw std::invalid_argument("train: float64 counter expected");
           counter = t[4].cast<py::array_t<double>>();
@@ -159,10 +194,24 @@ PYBIND11_MODULE(_cpu, m) {
           ctr = {c[0], c[1], c[2]};
           o.counter = &ctr;
         }
+        f64arr rate_table;
+        if (!rates.is_none()) {
+          rate_table = rates.cast<f64arr>();
+          o.rates = rate_table.data();
+          o.nrates = rate_table.size();
+        }
+        o.clip_norm = clip_norm;
+        std::vector<double> ulog;
+        if (!update_log.is_none()) o.update_log = &ulog;
         std::vector<double> losses;
         {
           py::gil_scoped_release r;
           losses = cme::cpu::train(v, X.data(), labels.data(), (int)X.shape(0), o);
+        }
+        if (!update_log.is_none()) {
+          py::list out = update_log.cast<py::list>();
+          for (size_t i = 0; i + 4 <= ulog.size(); i += 4)
+            out.append(py::make_tuple((int64_t)ulog[i], ulog[i + 1], ulog[i + 2], ulog[i + 3]));
         }
         if (o.counter) {
           double* c = mut(counter);
@@ -173,18 +222,21 @@ PYBIND11_MODULE(_cpu, m) {
       py::arg("W1"), py::arg("b1"), py::arg("W2"), py::arg("b2"), py::arg("X"), py::arg("labels"), py::arg("lr"),
       py::arg("reg"), py::arg("epochs"), py::arg("batch"), py::arg("print_every") = 0, py::arg("debug") = false,
       py::arg("outdir") = "Outputs", py::arg("shift") = true, py::arg("ckpt_precision") = 12,
-      py::arg("iter0") = 0, py::arg("optim") = py::none());
+      py::arg("iter0") = 0, py::arg("optim") = py::none(), py::arg("rates") = py::none(), py::arg("clip_norm") = 0.0,
+      py::arg("update_log") = py::none());
 
   // one update of the stateful rules (csrc/mlp/optim.h, the header the kernel compiles) on float32 or float64 arrays,
-  // in place: kind 0 = momentum / Nesterov (s1 = v), 1 = adam (s1 = m, s2 = s); hyper = (lr, mu, nesterov, beta1,
+  // in place: kind 0 = momentum / Nesterov (s1 = v), 1 = adam (s1 = m, s2 = s), 2 = the stateless sgd rule (s1 = None:
+  // what plain SGD runs under a schedule or clipping); hyper = (lr, mu, nesterov, beta1,
   // beta2, eps); t = the updates applied so far, b1p / b2p the running products b1^t, b2^t (None: formed by t
   // multiplications).  Returns the advanced (t, b1p, b2p).
   m.def(
       "optim_step",
-      [](int kind, py::object hyper, py::array params, py::array grads, py::array s1, py::object s2, int64_t t,
+      [](int kind, py::object hyper, py::array params, py::array grads, py::object s1, py::object s2, int64_t t,
          py::object b1p, py::object b2p) {
         const cme::OptimHyper h = hyper_of(hyper);
-        if (kind != cme::kMomentum && kind != cme::kAdam) throw std::invalid_argument("optim_step: kind 0 or 1");
+        if (kind != cme::kMomentum && kind != cme::kAdam && kind != cme::kSgd)
+          throw std::invalid_argument("optim_step: kind 0, 1 or 2");
         cme::OptimCounter c;
         if (b1p.is_none() || b2p.is_none()) {
           for (int64_t i = 0; i < t; ++i) cme::optim_advance(c, h);
@@ -195,7 +247,11 @@ PYBIND11_MODULE(_cpu, m) {
         const bool f32 = params.dtype().is(py::dtype::of<float>());
         if (!f32 && !params.dtype().is(py::dtype::of<double>()))
           throw std::invalid_argument("optim_step: float32 or float64 arrays expected");
-        std::vector<py::array> arrs = {params, grads, s1};
+        std::vector<py::array> arrs = {params, grads};
+        if (kind != cme::kSgd) {
+          if (s1.is_none()) throw std::invalid_argument("optim_step: momentum and adam need s1");
+          arrs.push_back(s1.cast<py::array>());
+        }
         if (kind == cme::kAdam) {
           if (s2.is_none()) throw std::invalid_argument("optim_step: adam needs s2");
           arrs.push_back(s2.cast<py::array>());
@@ -211,6 +267,11 @@ PYBIND11_MODULE(_cpu, m) {
           using T = decltype(tag);
           T* p = static_cast<T*>(arrs[0].mutable_data());
           const T* g = static_cast<const T*>(arrs[1].data());
+          if (kind == cme::kSgd) {
+            const auto k = cme::sgd_coef<T>(h);
+            for (py::ssize_t i = 0; i < n; ++i) cme::sgd_update(p[i], g[i], k);
+            return;
+          }
           T* a = static_cast<T*>(arrs[2].mutable_data());
           if (kind == cme::kMomentum) {
             const auto k = cme::momentum_coef<T>(h);
@@ -225,8 +286,52 @@ PYBIND11_MODULE(_cpu, m) {
         else run(double{});
         return py::make_tuple((int64_t)c.t, c.b1p, c.b2p);
       },
-      py::arg("kind"), py::arg("hyper"), py::arg("params"), py::arg("grads"), py::arg("s1"), py::arg("s2") = py::none(),
-      py::arg("t") = 0, py::arg("b1p") = py::none(), py::arg("b2p") = py::none());
+      py::arg("kind"), py::arg("hyper"), py::arg("params"), py::arg("grads"), py::arg("s1") = py::none(),
+      py::arg("s2") = py::none(), py::arg("t") = 0, py::arg("b1p") = py::none(), py::arg("b2p") = py::none());
+
+  // gradient-norm clipping on the host (csrc/mlp/clip.h, the header the kernels compile).  grad_sumsq: the partial
+  // sums of squares of the segments [(offset, size), ...] of a float32 / float64 array, one per workgroup of the
+  // kernel's grid, and the norm the apply launch forms from them.  grad_clip: scales the WHOLE array in place by
+  // T(coef) when coef = clip_norm / (norm + 1e-6) < 1 (the apply launch scales every element it reads) and returns
+  // (norm, coef).  window_rate: lr times the factor the apply launch reads for update t from the window (t0, factors).
+  m.def("clip_grid", &cme::clip_grid, py::arg("count"));
+  m.def(
+      "grad_sumsq",
+      [](py::array g, std::vector<std::pair<int64_t, int64_t>> segments) {
+        auto r = sumsq_of(g, segs_of(segments, g.size()));
+        return py::make_tuple(r.first, std::sqrt(r.second));
+      },
+      py::arg("g"), py::arg("segments"));
+  m.def(
+      "grad_clip",
+      [](py::array g, std::vector<std::pair<int64_t, int64_t>> segments, double clip_norm) {
+        if (!(clip_norm > 0.0)) throw std::invalid_argument("grad_clip: clip_norm must be > 0");
+        if (!g.writeable()) throw std::invalid_argument("grad_clip: a writable array expected");
+        const cme::ClipCoef c = cme::clip_coef(sumsq_of(g, segs_of(segments, g.size())).second, clip_norm);
+        if (c.clipped) {
+          const py::ssize_t n = g.size();
+          if (g.dtype().is(py::dtype::of<float>())) {
+            float* p = static_cast<float*>(g.mutable_data());
+            for (py::ssize_t i = 0; i < n; ++i) p[i] = cme::clip_scale(p[i], (float)c.coef);
+          } else {
+            double* p = static_cast<double*>(g.mutable_data());
+            for (py::ssize_t i = 0; i < n; ++i) p[i] = cme::clip_scale(p[i], c.coef);
+          }
+        }
+        return py::make_tuple(c.norm, c.coef);
+      },
+      py::arg("g"), py::arg("segments"), py::arg("clip_norm"));
+  m.def(
+      "window_rate",
+      [](double lr, double t0, f64arr factors, int64_t t) {
+        if (factors.size() < 1) throw std::invalid_argument("window_rate: at least one factor");
+        std::vector<double> w(cme::kWindowHeader + factors.size());
+        w[0] = t0;
+        w[1] = (double)factors.size();
+        std::copy(factors.data(), factors.data() + factors.size(), w.begin() + cme::kWindowHeader);
+        return cme::window_rate(lr, w.data(), (int)factors.size(), (double)t);
+      },
+      py::arg("lr"), py::arg("t0"), py::arg("factors"), py::arg("t"));
 
   // the per-epoch shuffle's order (csrc/mlp/shuffle.h, the header the gather kernel compiles): sample i of the
   // shuffled set is source sample perm[i]; key = the iteration counter at the epoch start

@@ -14,6 +14,7 @@
 #include "mlp/mlp_kernels.h"
 #include "mlp/mlp_split.h"
 #include "mlp/mlp_step.h"
+#include "mlp/clip.h"
 #include "mlp/optim.h"
 #include "mlp/shuffle.h"
 #include "suite/suite_kernels.h"
@@ -316,6 +317,48 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       py::arg("beta2"), py::arg("eps"), py::arg("params"), py::arg("grads"), py::arg("s1"), py::arg("s2"),
       py::arg("count"), py::arg("planes") = 0, py::arg("np") = 0, py::arg("w1n") = 0, py::arg("status") = 0,
       py::arg("rec") = 0, py::arg("nrec") = 0, py::arg("stream") = 0);
+  // the extended apply launch: optim_step's arguments by the same names, plus kind 2 = the stateless sgd rule (s1 = 0),
+  // window = the schedule window {t0, n, f[0 .. n)} with room for wcap factors (0: the rate is lr), partials / npart /
+  // clip_norm = the sum-of-squares partials of grad_sumsq and the threshold (clip_norm 0: no clipping), last = the
+  // 4-double last-update record {t, lr_t, grad_norm, clip_coef} (0: none)
+  m.def(
+      "optim_apply",
+      [](int dt, int kind, double lr, double mu, int nesterov, double beta1, double beta2, double eps,
+         uintptr_t params, uintptr_t grads, uintptr_t s1, uintptr_t s2, int64_t count, uintptr_t planes, int np,
+         int64_t w1n, uintptr_t status, uintptr_t rec, int nrec, uintptr_t window, int wcap, uintptr_t partials,
+         int npart, double clip_norm, uintptr_t last, uintptr_t s) {
+        cme::OptimArgs a;
+        a.dtype = dt; a.kind = kind;
+        a.h.lr = lr; a.h.mu = mu; a.h.nesterov = nesterov; a.h.beta1 = beta1; a.h.beta2 = beta2; a.h.eps = eps;
+        a.params = P<void>(params); a.grads = P<const void>(grads); a.s1 = P<void>(s1); a.s2 = P<void>(s2);
+        a.count = count; a.planes = P<void>(planes); a.np = np; a.w1n = w1n; a.status = P<const void>(status);
+        a.rec = P<double>(rec); a.nrec = nrec;
+        cme::OptimExt x;
+        x.window = P<const double>(window); x.wcap = wcap; x.partials = P<const double>(partials); x.npart = npart;
+        x.clip_norm = clip_norm; x.last = P<double>(last);
+        cme::mlp_optim_apply(a, x, P<void>(s));
+      },
+      py::arg("dt"), py::arg("kind"), py::arg("lr"), py::arg("mu"), py::arg("nesterov"), py::arg("beta1"),
+      py::arg("beta2"), py::arg("eps"), py::arg("params"), py::arg("grads"), py::arg("s1"), py::arg("s2"),
+      py::arg("count"), py::arg("planes") = 0, py::arg("np") = 0, py::arg("w1n") = 0, py::arg("status") = 0,
+      py::arg("rec") = 0, py::arg("nrec") = 0, py::arg("window") = 0, py::arg("wcap") = 0, py::arg("partials") = 0,
+      py::arg("npart") = 0, py::arg("clip_norm") = 0.0, py::arg("last") = 0, py::arg("stream") = 0);
+  // gradient-norm clipping (csrc/mlp/clip.h): the sum of squares of the segments [(offset, size), ...] of the bucket
+  // (`arena` elements) into clip_grid(sum of sizes) partials
+  m.def("clip_grid", &cme::clip_grid, py::arg("count"));
+  m.def(
+      "grad_sumsq",
+      [](int dt, uintptr_t grads, int64_t arena, std::vector<std::pair<int64_t, int64_t>> segments, uintptr_t partials,
+         int npart, uintptr_t s) {
+        if (segments.empty() || segments.size() > cme::kClipMaxSegs)
+          throw std::invalid_argument("grad_sumsq: 1 .. 4 (offset, size) segments");
+        cme::ClipSegs sg;
+        sg.n = static_cast<int>(segments.size());
+        for (int i = 0; i < sg.n; ++i) { sg.off[i] = segments[i].first; sg.size[i] = segments[i].second; }
+        cme::mlp_grad_sumsq(dt, P<const void>(grads), arena, sg, P<double>(partials), npart, P<void>(s));
+      },
+      py::arg("dt"), py::arg("grads"), py::arg("arena"), py::arg("segments"), py::arg("partials"), py::arg("npart"),
+      py::arg("stream") = 0);
 
   bind_suite(m);
   bind_comm(m);

@@ -10,6 +10,7 @@
 #include <stdexcept>
 
 #include "io.h"
+#include "mlp/clip.h"
 
 namespace cme::cpu {
 
@@ -176,6 +177,15 @@ std::vector<double> train(NetView net, const double* X, const int* labels, int N
   if (B <= 0) throw std::invalid_argument("batch size must be positive");
   if (o.optim_kind >= 0 && (o.optim_kind > kAdam || !o.s1 || !o.counter || (o.optim_kind == kAdam && !o.s2)))
     throw std::invalid_argument("train: a stateful optimizer needs its kind, state buffers and counter");
+  const bool policy = o.rates != nullptr || o.clip_norm > 0.0;
+  const int64_t P64 = P, H64 = H, C64 = C;
+  const int64_t total = H64 * P64 + H64 + C64 * H64 + C64;
+  if (policy && !o.counter) throw std::invalid_argument("train: a schedule or clipping needs the update counter");
+  if (o.rates && o.nrates < (int64_t)o.epochs * ((N + B - 1) / B))
+    throw std::invalid_argument("train: the rate table must hold one rate per update of the call");
+  if (!(o.clip_norm >= 0.0)) throw std::invalid_argument("train: clip_norm must be >= 0");
+  std::vector<double> flat(o.clip_norm > 0.0 ? total : 0), partials(kClipMaxGrid);
+  int64_t upd = 0;
   std::vector<double> a1((size_t)B * H), yc((size_t)B * C);
   std::vector<double> dW1((size_t)H * P), db1(H), dW2((size_t)C * H), db2(C);
   std::vector<double> losses;
@@ -195,14 +205,49 @@ std::vector<double> train(NetView net, const double* X, const int* labels, int N
         std::printf("Loss at iteration %d of epoch %d/%d = %.10g\n", iter, epoch, o.epochs, l);
         std::fflush(stdout);
       }
-      if (o.optim_kind < 0) {
+      const double rate = o.rates ? o.rates[upd] : o.lr;
+      ++upd;
+      ClipCoef cc{std::nan(""), 1.0, 0};
+      if (o.clip_norm > 0.0) {  // the global norm in clip.h's order over the unpadded [dW1|db1|dW2|db2]
+        ClipSegs sg;
+        sg.n = 4;
+        const double* src[4] = {dW1.data(), db1.data(), dW2.data(), db2.data()};
+        const int64_t cnt[4] = {H64 * P64, H64, C64 * H64, C64};
+        int64_t base = 0;
+        for (int q = 0; q < 4; base += cnt[q], ++q) {
+          sg.off[q] = base;
+          sg.size[q] = cnt[q];
+          std::copy(src[q], src[q] + cnt[q], flat.begin() + base);
+        }
+        cc = clip_coef(clip_host_sumsq<double>(flat.data(), sg, partials.data()), o.clip_norm);
+        if (cc.clipped) {
+          double* dst[4] = {dW1.data(), db1.data(), dW2.data(), db2.data()};
+          for (int q = 0; q < 4; ++q)
+            for (int64_t i = 0; i < cnt[q]; ++i) dst[q][i] = clip_scale(dst[q][i], cc.coef);
+        }
+      }
+      if (o.update_log && o.counter) {
+        const double rec[4] = {o.counter->t, rate, cc.norm, cc.coef};
+        o.update_log->insert(o.update_log->end(), rec, rec + 4);
+      }
+      if (o.optim_kind < 0 && policy) {
+        OptimHyper h = o.hyper;
+        h.lr = rate;
+        optim_advance(*o.counter, h);
+        const auto k = sgd_coef<double>(h);
+        double* prm[4] = {net.W1, net.b1, net.W2, net.b2};
+        const double* grd[4] = {dW1.data(), db1.data(), dW2.data(), db2.data()};
+        const int64_t cnt[4] = {H64 * P64, H64, C64 * H64, C64};
+        for (int q = 0; q < 4; ++q)
+          for (int64_t i = 0; i < cnt[q]; ++i) sgd_update(prm[q][i], grd[q][i], k);
+      } else if (o.optim_kind < 0) {
         for (int64_t i = 0; i < (int64_t)H * P; ++i) net.W1[i] -= o.lr * dW1[i];
         for (int64_t i = 0; i < (int64_t)C * H; ++i) net.W2[i] -= o.lr * dW2[i];
         for (int i = 0; i < H; ++i) net.b1[i] -= o.lr * db1[i];
         for (int i = 0; i < C; ++i) net.b2[i] -= o.lr * db2[i];
       } else {
         OptimHyper h = o.hyper;
-        h.lr = o.lr;
+        h.lr = rate;
         optim_advance(*o.counter, h);
         double* prm[4] = {net.W1, net.b1, net.W2, net.b2};
         const double* grd[4] = {dW1.data(), db1.data(), dW2.data(), db2.data()};

@@ -61,6 +61,15 @@ struct TrainOpts {
   double* s1 = nullptr;
   double* s2 = nullptr;
   OptimCounter* counter = nullptr;
+  // a learning-rate schedule and gradient-norm clipping (mlp/optim.h kSgd, mlp/clip.h): rates = the rate of every
+  // update of this call, epochs * ceil(N / B) doubles (null: lr throughout); clip_norm > 0 clips the global norm of
+  // [dW1|db1|dW2|db2] in clip.h's order.  Either one makes plain SGD (optim_kind -1) run the kSgd rule, which then
+  // needs `counter` too.  update_log (optional): {t, rate, grad_norm, clip_coef} appended per update (norm NaN and
+  // coef 1 without clipping).
+  const double* rates = nullptr;
+  int64_t nrates = 0;
+  double clip_norm = 0.0;
+  std::vector<double>* update_log = nullptr;
 };
 
 // Minibatch SGD (neural_network.cpp:219-279): ceil(N/B) batches per epoch, the

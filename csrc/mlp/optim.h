@@ -1,4 +1,5 @@
-// The stateful update rules (momentum / Nesterov, Adam) of the flat parameter arena, one header for host and device:
+// The update rules of the apply launch (momentum / Nesterov, Adam, and the stateless kSgd that plain SGD runs when a
+// learning-rate schedule or gradient clipping is set) of the flat parameter arena, one header for host and device:
 // the kernel (optim.hip), the CPU binding `_cpu.optim_step` (the kernel tests' bitwise oracle and the torch backend's
 // implementation) and the fp64 oracle trainer (cpu/mlp_cpu.cpp) all evaluate these functions.
 //
@@ -8,6 +9,8 @@
 //   adam      m = b1 m + (1 - b1) g;  s = b2 s + (1 - b2) g g;
 //             p -= (lr / (1 - b1^t)) m / (sqrt(s) / sqrt(1 - b2^t) + eps)
 //             (torch.optim.Adam without weight decay or amsgrad; t counts the applied updates from 1)
+//   sgd       p = fma(-lr, g, p)   (torch.optim.SGD; no state buffer)
+// lr is the rate of THIS update: h.lr times the schedule's factor when the launch has a schedule window (below).
 //
 // Host (g++) and device (hipcc) produce the same bits: only + - * / sqrt fma, every fused multiply-add written as an
 // explicit fma, contraction switched off under clang (g++ builds here target no FMA instruction set, so it cannot
@@ -26,7 +29,7 @@
 
 namespace cme {
 
-enum OptimKind { kMomentum = 0, kAdam = 1 };
+enum OptimKind { kMomentum = 0, kAdam = 1, kSgd = 2 };
 
 struct OptimHyper {
   double lr = 0.0;
@@ -75,6 +78,47 @@ __host__ __device__ inline void momentum_update(T& p, T& v, T g, const MomentumC
 }
 
 template <typename T>
+struct SgdCoef {
+  T nlr;  // -lr
+};
+
+template <typename T>
+__host__ __device__ inline SgdCoef<T> sgd_coef(const OptimHyper& h) {
+  return {static_cast<T>(-h.lr)};
+}
+
+template <typename T>
+__host__ __device__ inline void sgd_update(T& p, T g, const SgdCoef<T>& c) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  p = optim_fma(c.nlr, g, p);
+}
+
+// ---- the schedule window ----------------------------------------------------------------------------------------
+// The factor of update t (0-based: the count of applied updates BEFORE this one) comes from a device buffer of fp64
+// doubles {t0, n, f[0 .. n)} with room for `cap` factors: i = t - t0 clamped into [0, n - 1] (n itself clamped into
+// [1, cap], so no index leaves the buffer whatever the buffer holds), lr_t = h.lr * f[i] in fp64.  The host refills the
+// buffer in place between launches (never during a capture), so a captured graph follows the schedule.
+constexpr int kWindowHeader = 2;  // doubles before f[0]
+
+__host__ __device__ inline int window_index(double t, double t0, double n, int cap) {
+  int m = 1;
+  if (n >= 2.0) m = n >= static_cast<double>(cap) ? cap : static_cast<int>(n);
+  const double d = t - t0;
+  int i = 0;
+  if (d >= 1.0) i = d >= static_cast<double>(m - 1) ? m - 1 : static_cast<int>(d);
+  return i;
+}
+
+__host__ __device__ inline double window_rate(double lr, const double* w, int cap, double t) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  return lr * w[kWindowHeader + window_index(t, w[0], w[1], cap)];
+}
+
+template <typename T>
 struct AdamCoef {
   T b1, b2, omb1, omb2;  // beta1, beta2, 1 - beta1, 1 - beta2
   T nstep;               // -lr / (1 - b1^t)
@@ -116,7 +160,7 @@ __host__ __device__ inline void adam_update(T& p, T& m, T& s, T g, const AdamCoe
 
 // ---- the launch (optim.hip) ----------------------------------------------------------------------------------
 // One launch over the flat arena [W1|b1|W2|b2|status] of `count` elements of type dtype (0: f32, 1: f64):
-//   params, grads, s1 (momentum: v; adam: m), s2 (adam: s; else null) -- `count` elements each;
+//   params, grads, s1 (momentum: v; adam: m; sgd: null), s2 (adam: s; else null) -- `count` elements each;
 //   planes: np (0 / 1 / 3) bf16 planes [np][w1n] of the first w1n parameters (f32 only): 3 = the exact split3
 //     planes, 1 = split1 or the bf16 path's shadow -- as sgd_planes_kernel / sgd_flat treat them;
 //   status: the gradient bucket's status element (dtype), or null: non-zero -> the launch changes nothing, neither
@@ -125,6 +169,13 @@ __host__ __device__ inline void adam_update(T& p, T& m, T& s, T g, const AdamCoe
 //     the same kernel arguments, so the launch reads and advances the count itself; a single shared record would
 //     race with a workgroup scheduled late, so every workgroup owns a copy (thread 0 reads it, broadcasts through
 //     LDS, writes the advanced one back) and elements are assigned to workgroups by index alone.
+// The extended form (mlp_optim_apply: OptimArgs plus OptimExt; kind kSgd always takes it):
+//   window: the schedule window above (wcap = its capacity in factors), or null: lr_t = h.lr;
+//   clip_norm > 0: partials = the npart = clip_grid(...) partial sums of squares the launch before this one left
+//     (clip.h); every workgroup combines them in the header's order and scales the gradient it reads by T(coef) when
+//     coef < 1;
+//   last: 4 doubles {t, lr_t, grad_norm, clip_coef} written by workgroup 0 (NaN, 1 without clipping), or null.
+// mlp_optim_step is the launch as it stood: the same kernel signature, the same code, the same bits.
 // Plain vector stores only; no workgroup waits for another.
 struct OptimArgs {
   int dtype = 0;
@@ -141,8 +192,18 @@ struct OptimArgs {
   double* rec = nullptr;
   int nrec = 0;
 };
+struct OptimExt {
+  const double* window = nullptr;
+  int wcap = 0;
+  const double* partials = nullptr;
+  int npart = 0;
+  double clip_norm = 0.0;
+  double* last = nullptr;
+};
+constexpr int kOptimLastWords = 4;
 constexpr int kOptimRecWords = 4;  // doubles per record (32 bytes)
 int optim_grid(int64_t count);     // workgroups (= records) of the launch over `count` elements, any dtype
 void mlp_optim_step(const OptimArgs& a, void* stream);  // stream: a hipStream_t
+void mlp_optim_apply(const OptimArgs& a, const OptimExt& x, void* stream);
 
 }  // namespace cme
