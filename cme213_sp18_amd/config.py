@@ -68,6 +68,11 @@ class TrainConfig:
     warmup: int = 0             # --warmup: linear warm-up over that many units (needs --lr-schedule)
     warmup_start: float = 0.0   # --warmup-start: the factor of the first unit
     clip_norm: float | None = None  # --clip-norm: clip the gradient's global norm (torch's clip_grad_norm_)
+    keep_best: str = ""         # --keep-best loss | accuracy: keep the best evaluation's weights on the device (dp)
+    patience: int | None = None  # --patience N: stop after N + 1 non-improving evaluations in a row (needs --keep-best)
+    min_delta: float = 0.0      # --min-delta D: an evaluation improves only by more than D
+    stop_check_every: int = 0   # --stop-check-every K: the host looks at the stop flag after every K-th evaluated epoch
+    restore_best: bool = False  # --restore-best: the best weights become the final ones (outputs and checkpoint)
 
     @property
     def schedule(self):
@@ -186,6 +191,21 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--clip-norm", type=float,
                     help="clip the gradient's global L2 norm at this value before the update (torch's "
                          "clip_grad_norm_, the regulariser included; formed on the device; data parallel only)")
+    ap.add_argument("--keep-best", choices=["loss", "accuracy"],
+                    help="behind every --eval-every evaluation decide on the device whether it is the best so far "
+                         "(validation loss or accuracy) and keep those weights there; `best` event in --log-json, "
+                         "<ckpt>/best/ in checkpoints (data parallel only)")
+    ap.add_argument("--patience", type=int,
+                    help="early stopping: tolerate N non-improving evaluations in a row and stop on number N + 1 "
+                         "(0: the first one); needs --keep-best")
+    ap.add_argument("--min-delta", type=float,
+                    help="an evaluation counts as an improvement only when it beats the best by more than D (default 0)")
+    ap.add_argument("--stop-check-every", type=int,
+                    help="the host reads the device's stop flag after every K-th evaluated epoch (a sync and a 64-byte "
+                         "read) and ends the run when it is set; 0 = only where the host syncs on the epoch anyway")
+    ap.add_argument("--restore-best", action="store_true", default=None,
+                    help="after training, make the best weights the current ones: the precision, the predictions and "
+                         "the final checkpoint are those of the best evaluation")
     ap.add_argument("--gpus", type=int,
                     help="number of ranks, one per GPU (the reference's mpirun -np N); started here when no "
                          "launcher started this process")
@@ -224,6 +244,19 @@ def parse_config(argv=None) -> TrainConfig:
                                    if k != "lr_schedule"):
         ap.error("--lr-gamma, --lr-step-size, --lr-total, --lr-end-factor, --lr-min-factor, --lr-unit, --warmup and "
                  "--warmup-start need --lr-schedule")
+    # keeping the best weights acts on the device-side evaluations of the data-parallel trainer
+    best_flags = [f for f, on in (("--patience", cfg.patience is not None), ("--min-delta", "min_delta" in explicit),
+                                  ("--stop-check-every", "stop_check_every" in explicit),
+                                  ("--restore-best", cfg.restore_best)) if on]
+    if best_flags and not cfg.keep_best:
+        ap.error(f"{', '.join(best_flags)} need(s) --keep-best loss | accuracy")
+    if cfg.keep_best and cfg.parallel == "tp":
+        ap.error("--keep-best acts on the device-side evaluation, which is data-parallel only; it needs --parallel dp")
+    if cfg.keep_best and not cfg.eval_every > 0:
+        ap.error("--keep-best acts on the evaluations: it needs --eval-every N > 0")
+    if cfg.keep_best and ((cfg.patience is not None and cfg.patience < 0) or cfg.min_delta < 0
+                          or cfg.stop_check_every < 0):
+        ap.error("--patience, --min-delta and --stop-check-every must be >= 0")
     try:
         cfg.optim  # the hyper-parameters' ranges (optim.Optimizer validates)
         cfg.schedule

@@ -176,6 +176,9 @@ class MlpEngine:
         # partials (csrc/mlp/clip.h) and the last-update record {t, lr_t, grad_norm, clip_coef}
         self.schedule, self.clip_norm = None, 0.0
         self.sched_win = self._win_host = self.clip_partials = self.opt_last = None
+        # keeping the best validation weights (enable_keep_best): None = nothing allocated, nothing launched; else the
+        # rule, the best arena, the per-workgroup records (csrc/mlp/best.h) and, for data parallel, the [R][3] rows
+        self._best = None
 
     def _configure_path(self):
         dev = self.device
@@ -1101,3 +1104,180 @@ class MlpEngine:
     def evaluate(self, slot: int = 0, first: int = 0, count: int | None = None) -> dict:
         self.enqueue_eval(slot, first, count)
         return self.read_eval(slot)
+
+    # ------------------------------------------------------- keep the best weights
+    BEST_MONITORS = {"loss": 0, "accuracy": 1}
+    BEST_FIELDS = ("evals", "best_index", "best_metric", "bad", "stopped", "stop_index", "last_metric")
+
+    @staticmethod
+    def _best_rule(monitor, min_delta, patience) -> tuple:
+        if monitor not in MlpEngine.BEST_MONITORS:
+            raise ValueError(f"monitor must be one of {list(MlpEngine.BEST_MONITORS)}")
+        min_delta = float(min_delta)
+        if not min_delta >= 0.0:
+            raise ValueError("min_delta must be >= 0")
+        if patience is not None and int(patience) < 0:
+            raise ValueError("patience must be >= 0 (None: never stop)")
+        return monitor, min_delta, -1 if patience is None else int(patience)
+
+    @property
+    def best_count(self) -> int:
+        """Elements of the best arena: the parameter arena [W1|b1|W2|b2] without the status element."""
+        return int(self.layout.status)
+
+    def enable_keep_best(self, monitor: str = "loss", min_delta: float = 0.0, patience: int | None = None,
+                         ranks: int = 1) -> None:
+        """Keep the parameters of the best evaluation on the device (csrc/mlp/best.h): allocates the best arena (the
+        parameter dtype; bf16 mode's masters are fp32, the bf16 planes are derived state and not kept), the records
+        (one per workgroup of the kernel's fixed grid on the hip backend, one otherwise) and, for ``ranks`` > 1, the
+        [ranks][3] rows of a data-parallel decision; nothing else ever allocates.  ``patience`` = p tolerates p
+        non-improving evaluations and stops on number p + 1 (0: the first one; None: never).  Calling it again with
+        the same rule is a no-op; a different rule raises unless reset_best() was called first."""
+        rule = self._best_rule(monitor, min_delta, patience)
+        ranks = int(ranks)
+        if ranks < 1:
+            raise ValueError("ranks must be >= 1")
+        b = self._best
+        if b is not None:
+            if b["rule"] == rule and b["ranks"] == ranks:
+                return
+            if not b["fresh"]:
+                raise RuntimeError(f"keep-best is enabled with the rule {b['rule']}; reset_best() before changing it "
+                                   f"to {rule}")
+        dev = self.device
+        nrec = int(hip().best_grid(self.best_count)) if self.backend == "hip" else 1
+        self._best = dict(rule=rule, ranks=ranks, fresh=True,
+                          arena=torch.zeros(self.best_count, dtype=self.pdt, device=dev),
+                          rec=torch.zeros(nrec, 8, dtype=torch.float64, device=dev),
+                          rows=torch.zeros(ranks, 3, dtype=torch.float64, device=dev) if ranks > 1 else None)
+        self.reset_best()
+
+    def _best_set(self) -> dict:
+        if self._best is None:
+            raise RuntimeError("enable_keep_best() first")
+        return self._best
+
+    @property
+    def best_rows(self):
+        """The [ranks][3] device buffer of a data-parallel decision (None for one rank)."""
+        return self._best_set()["rows"]
+
+    def reset_best(self) -> None:
+        """Forget the best: the records back to the start state {0, -1, NaN, 0, 0, -1, NaN, 0}, the best arena zeroed.
+        The rule may be changed afterwards."""
+        b = self._best_set()
+        with torch.no_grad():
+            b["arena"].zero_()
+            b["rec"].copy_(torch.from_numpy(cpu().best_start()).expand_as(b["rec"]))
+        b["fresh"] = True
+
+    def _slot_triple(self, ev, slot: int) -> np.ndarray:
+        w = ev["stats"][int(slot), :3].cpu()
+        return np.array([[float(int(w[0])), float(int(w[1])), float(w[2:3].view(torch.float64)[0])]], np.float64)
+
+    def pack_best_rows(self, slot: int, rank: int) -> None:
+        """This rank's {n, correct, loss_sum} of stats slot ``slot`` into row ``rank`` of best_rows, zero into every
+        other row: a SUM all-reduce of the buffer is then an exact all-gather.  On the current stream; no host read on
+        the hip backend."""
+        b = self._best_set()
+        ev = self._eval_set(slot)
+        rows = b["rows"]
+        if rows is None:
+            raise RuntimeError("enable_keep_best(ranks=R) with R > 1 first")
+        if not 0 <= int(rank) < rows.shape[0]:
+            raise IndexError(f"rank {rank} outside [0, {rows.shape[0]})")
+        if self.backend == "hip":
+            hip().mlp_best_pack(ev["stats"].data_ptr() + int(slot) * ev["stats"].shape[1] * 8, rows.data_ptr(),
+                                int(rows.shape[0]), int(rank), torch.cuda.current_stream(self.device).cuda_stream)
+            return
+        with torch.no_grad():
+            rows.zero_()
+            rows[int(rank)].copy_(torch.from_numpy(self._slot_triple(ev, slot)[0]))
+
+    def enqueue_keep_best(self, slot: int, rows=None) -> None:
+        """One decision on the current stream, behind enqueue_eval(slot): from stats slot ``slot`` (one process) or from
+        ``rows`` (a [R][3] float64 tensor of {n, correct, loss_sum} per rank, summed in rank order; on the hip backend
+        a device tensor that stays alive until the launch has run -- best_rows is the resident one).  When the metric
+        improves on the best so far, the parameter arena is copied into the best arena; every record advances.  No host
+        read, no sync, no allocation on the hip backend: legal under stream capture."""
+        b = self._best_set()
+        ev = self._eval_set(slot)
+        monitor, min_delta, patience = b["rule"]
+        code = self.BEST_MONITORS[monitor]
+        b["fresh"] = False
+        if rows is not None and (rows.dtype != torch.float64 or rows.ndim != 2 or rows.shape[1] != 3
+                                 or rows.shape[0] < 1 or not rows.is_contiguous()):
+            raise ValueError("rows must be a contiguous [R][3] float64 tensor, R >= 1")
+        if self.backend == "hip":
+            if rows is not None and rows.device != self.device:
+                raise ValueError("rows must live on the engine's device")
+            hip().mlp_keep_best(0 if self.pdt == torch.float32 else 1, code, min_delta, patience,
+                                self.params.data_ptr(), b["arena"].data_ptr(), self.best_count, b["rec"].data_ptr(),
+                                int(b["rec"].shape[0]),
+                                0 if rows is not None else
+                                ev["stats"].data_ptr() + int(slot) * ev["stats"].shape[1] * 8,
+                                rows.data_ptr() if rows is not None else 0,
+                                int(rows.shape[0]) if rows is not None else 1,
+                                torch.cuda.current_stream(self.device).cuda_stream)
+            return
+        with torch.no_grad():
+            triples = rows.cpu().numpy() if rows is not None else self._slot_triple(ev, slot)
+            rec, improved = cpu().best_decide(b["rec"][0].cpu().numpy(), code, min_delta, patience, triples)
+            b["rec"].copy_(torch.from_numpy(rec).expand_as(b["rec"]))
+            if improved:
+                b["arena"].copy_(self.params[:self.best_count])
+
+    def best_state(self) -> dict:
+        """Record 0 as a dict: evals, best_index, best_metric, bad, stopped, stop_index, last_metric (+ the rule:
+        monitor, min_delta, patience).  The one sync: a 64-byte read."""
+        b = self._best_set()
+        r = b["rec"][0].cpu().tolist()
+        monitor, min_delta, patience = b["rule"]
+        return {"evals": int(r[0]), "best_index": int(r[1]), "best_metric": r[2], "bad": int(r[3]),
+                "stopped": bool(r[4]), "stop_index": int(r[5]), "last_metric": r[6], "monitor": monitor,
+                "min_delta": min_delta, "patience": None if patience < 0 else patience}
+
+    def best_records(self) -> np.ndarray:
+        """Every workgroup's record as raw doubles [nrec][8] (tests and diagnostics).  Synchronises."""
+        return self._best_set()["rec"].cpu().numpy().copy()
+
+    def best_params(self):
+        """Host float64 copies (W1, b1, W2, b2) of the best weights, as get_params(); None before any best."""
+        b = self._best_set()
+        if float(b["rec"][0, 1].item()) < 0:
+            return None
+        return tuple(t.detach().to("cpu", torch.float64).numpy().copy() for t in self.layout.views(b["arena"]))
+
+    def restore_best(self) -> dict:
+        """Copy the best weights back into the parameter arena (a device copy) and re-derive the bf16 planes / shadow
+        of W1, as set_params does.  Raises when there is no best yet.  Returns best_state()."""
+        b = self._best_set()
+        st = self.best_state()
+        if st["best_index"] < 0:
+            raise RuntimeError("restore_best(): no evaluation has been accepted as the best yet")
+        with torch.no_grad():
+            self.params[:self.best_count].copy_(b["arena"])
+            self.refresh_shadow()
+        self.mark_planes_stale()
+        return st
+
+    def set_best_state(self, record, params=None) -> None:
+        """Resume: ``record`` = the 8 doubles of a record (or a best_state() dict), ``params`` = (W1, b1, W2, b2) of the
+        best weights (None: the arena is left as it is; required when the record holds a best)."""
+        b = self._best_set()
+        if isinstance(record, dict):
+            record = [record[k] for k in self.BEST_FIELDS] + [0.0]
+        rec = np.asarray([float(v) for v in record], np.float64).reshape(-1)
+        if rec.size != 8:
+            raise ValueError("a record is 8 doubles")
+        if rec[1] >= 0 and params is None:
+            raise ValueError("the record holds a best: its weights are required")
+        with torch.no_grad():
+            if params is not None:
+                for dst, src in zip(self.layout.views(b["arena"]), params):
+                    src = torch.as_tensor(np.asarray(src))
+                    if src.numel() != dst.numel():
+                        raise ValueError("best weights of another shape")
+                    dst.copy_(src.reshape(dst.shape).to(dst.dtype))
+            b["rec"].copy_(torch.from_numpy(rec).expand_as(b["rec"]))
+        b["fresh"] = False

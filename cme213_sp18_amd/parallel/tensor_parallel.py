@@ -307,13 +307,18 @@ class TensorParallelTrainer:
     # ------------------------------------------------------------------- train
     def train(self, epochs: int, lr: float, reg: float, print_every: int = 0, debug: bool = False,
               outdir: str = "Outputs", log=print, on_event=None, fault=None,
-              shuffle_seed: int | None = None) -> TrainStats:
+              shuffle_seed: int | None = None, keep_best: str | None = None, **best_kw) -> TrainStats:
         """Training loop with the data-parallel trainer's interface (loss every ``print_every`` steps,
         JSON-lines epoch events, ``fault=(rank, step)`` injection); graph-replayed epochs when no loss is
         printed.  ``debug`` (the reference's per-iteration CPU diff) is data-parallel only.  ``shuffle_seed``
         (default: the constructor's): the resident set -- whole on every rank -- is reordered on the device before
-        each epoch, as in DataParallelTrainer.train."""
+        each epoch, as in DataParallelTrainer.train.  ``keep_best`` (and patience / min_delta / stop_check_every) is
+        refused: it acts on the device-side evaluation, which is data-parallel only."""
         from .trainer import CommFailure, FaultInjected
+
+        if keep_best is not None or best_kw:
+            raise ValueError("tensor parallelism has no device-side evaluation: keep_best, patience, min_delta and "
+                             "stop_check_every need data parallelism (--parallel dp)")
 
         stats = TrainStats()
         plan = self.epoch_plan()

@@ -224,6 +224,12 @@ class TrainStats:
     losses: list = field(default_factory=list)
     # train(eval_every=k): one {epoch, iter, n, loss, accuracy, confusion} per evaluated epoch
     evals: list = field(default_factory=list)
+    # train(keep_best=...): {index, iter, epoch, metric, monitor, loss, accuracy} of the best evaluation so far (None
+    # before any; epoch None when the best dates from an earlier call, loss / accuracy None when this call did not read
+    # that evaluation), whether the device's rule has stopped, and the decision that stopped it (-1: none)
+    best: dict | None = None
+    stopped: bool = False
+    stop_index: int = -1
 
     @property
     def images_per_sec(self) -> float:
@@ -307,6 +313,9 @@ class DataParallelTrainer:
         self._graphs: dict = {}
         self._sharing = None
         self.iter = 0
+        # train(keep_best=...): the iteration counter behind every decision the device has taken, across calls (the
+        # device's record counts the decisions; the host remembers when each was taken)
+        self._best_iters: list = []
         # the all-gather forward + head launch waits for the other workgroups of its own launch: every
         # workgroup must be resident at once, which several processes sharing a GPU (each launch spinning
         # while the other's holds CUs) cannot promise -- one process per GPU keeps it
@@ -476,6 +485,9 @@ class DataParallelTrainer:
         if e.opt_rec is not None:  # ... and the same optimizer state and update count
             w = torch.cat([w] + [as_words(b.detach().reshape(-1)).to(torch.int64) for b in e.opt_bufs]
                           + [e.opt_rec[0].view(torch.int64)])
+        if e._best is not None:  # ... and the same best weights and decisions
+            w = torch.cat([w, as_words(e._best["arena"].detach().reshape(-1)).to(torch.int64),
+                           e._best["rec"][0].view(torch.int64)])
         idx = torch.arange(1, w.numel() + 1, device=w.device, dtype=torch.int64)
         # two position-weighted sums, folded below 2^52 so they travel exactly as float64
         h = [int(w.sum().item()) % (1 << 52), int(((w % 65521) * (idx % 65519)).sum().item()) % (1 << 52)]
@@ -784,6 +796,9 @@ class DataParallelTrainer:
                 (e.W1p.clone() if e.W1p is not None else None))
         if e.opt_rec is not None:  # the state buffers and every workgroup's counter record
             snap += ([b.clone() for b in e.opt_bufs], e.opt_rec.clone())
+        if e._best is not None:  # the best arena, every workgroup's record and the host's list of decisions
+            snap += ({"arena": e._best["arena"].clone(), "rec": e._best["rec"].clone(),
+                      "iters": len(self._best_iters)},)
         return snap
 
     def _restore(self, snap):
@@ -793,10 +808,14 @@ class DataParallelTrainer:
             e.W1g.copy_(snap[1])
         if snap[2] is not None:
             e.W1p.copy_(snap[2])
-        if len(snap) > 3:
+        if len(snap) > 3 and not isinstance(snap[3], dict):
             for b, src in zip(e.opt_bufs, snap[3]):
                 b.copy_(src)
             e.opt_rec.copy_(snap[4])
+        if isinstance(snap[-1], dict) and e._best is not None:
+            e._best["arena"].copy_(snap[-1]["arena"])
+            e._best["rec"].copy_(snap[-1]["rec"])
+            del self._best_iters[snap[-1]["iters"]:]
         e.mark_planes_stale()
 
     def capture(self, plan: EpochPlan, lr: float, reg: float) -> torch.cuda.CUDAGraph:
@@ -970,7 +989,8 @@ class DataParallelTrainer:
     # ---------------------------------------------------------------- train
     def train(self, epochs: int, lr: float, reg: float, print_every: int = 0, debug: bool = False,
               outdir: str = "Outputs", log=print, on_event=None, fault: tuple[int, int] | None = None,
-              diff_file=None, eval_every: int = 0, shuffle_seed: int | None = None) -> TrainStats:
+              diff_file=None, eval_every: int = 0, shuffle_seed: int | None = None, keep_best: str | None = None,
+              patience: int | None = None, min_delta: float = 0.0, stop_check_every: int = 0) -> TrainStats:
         """Full training loop (neural_network.cpp:446-555).  Eager steps where the
         host must look at a step (loss printing / debug diffs), graphs elsewhere.
 
@@ -1005,10 +1025,31 @@ class DataParallelTrainer:
         and a resumed run (count restored by set_optim_state) continues the sequence.  When the host looks at a step
         anyway (print_every), the loss event gains ``lr`` and ``grad_norm`` (engine.last_update()).
 
+        keep_best="loss" | "accuracy" (needs eval_every > 0): behind every evaluation one more launch decides on the
+        device whether that evaluation is the best so far (csrc/mlp/best.h: strict improvement by more than min_delta;
+        a tie keeps the earlier one) and, if so, copies the parameters into the best arena.  At R > 1 every rank packs
+        its {n, correct, loss_sum} into its row of a [R][3] buffer, a SUM all-reduce gathers the rows exactly and every
+        rank takes the same decision.  The record and the best arena live on the device across calls: train(2) +
+        train(2) equals train(4) in both, bitwise.  train() never restores by itself: restore_best() does.
+        ``patience`` = p tolerates p non-improving evaluations and stops on number p + 1 (0: the first one; None:
+        never).  The device cannot stop the host's loop: after the rule has stopped, further epochs still run, but no
+        later evaluation can replace the best, so the best weights and the record are exactly those of a run that had
+        stopped there.  The host looks at the flag whenever it already syncs on the epoch (on_event, print_every, debug,
+        the xGMI / all-gather checks) and, with stop_check_every=k > 0, after every k-th evaluated epoch (a sync and a
+        64-byte read); when it sees it, train() returns after that epoch with ``stats.stopped``.  Every rank reads its
+        own identical record, so all ranks leave together without a collective.  The iteration counter, the
+        parameters and the optimizer state after an early return are those of the epoch the host left at, not those of
+        the best or of the stopping evaluation.  ``TrainStats.best`` / ``stopped`` / ``stop_index`` report the record.
+
         With the xGMI all-reduce, every epoch ends with a collective check of the peer-wait error flag
         (assert_comm_ok): a timed-out wait raises CommFailure on every rank before another epoch runs."""
         from ..utils.checkpoint import write_diff_gpu_cpu
 
+        if keep_best is None and (patience is not None or stop_check_every or min_delta):
+            raise ValueError("patience, min_delta and stop_check_every need keep_best='loss' or 'accuracy'")
+        if keep_best is not None and not int(eval_every) > 0:
+            raise ValueError("train(keep_best=...) needs eval_every > 0: the rule acts on the evaluations")
+        stop_check_every = max(0, int(stop_check_every))
         stats = TrainStats()
         plan = self.epoch_plan()
         seed = self.shuffle_seed if shuffle_seed is None else int(shuffle_seed)
@@ -1026,6 +1067,10 @@ class DataParallelTrainer:
             if self.engine.eval_slots == 0:
                 raise RuntimeError("train(eval_every=...): load_eval() first")
             self.engine.reserve_eval_slots(max(1, n_ev))
+        if keep_best is not None:
+            self.engine.enable_keep_best(keep_best, min_delta, patience, ranks=self.R)
+        best_epochs: dict = {}  # decision index -> epoch of this call
+        stop_seen = [False]
         host_looks = on_event is not None or print_every > 0 or debug
         ev_meta: dict = {}  # slot -> (epoch, iter) of the evaluations enqueued
         ev_read: dict = {}  # slot -> record, for the slots read before the end
@@ -1046,9 +1091,22 @@ class DataParallelTrainer:
             if on_event is not None:
                 on_event({"event": "eval", "epoch": epoch, "iter": self.iter, "n": r["n"], "loss": r["loss"],
                           "accuracy": r["accuracy"]})
+
+        def best_enqueued(epoch: int) -> None:
+            """The decision behind this epoch's evaluation is on the stream: remember when it was taken and, where the
+            host syncs on the epoch anyway or stop_check_every asks for it, look at the stop flag."""
+            best_epochs[len(self._best_iters)] = epoch
+            self._best_iters.append(self.iter)
+            k = stop_check_every
+            if host_looks or xgmi_live or ag_live or (k and len(best_epochs) % k == 0):
+                stop_seen[0] = self.engine.best_state()["stopped"]
         dev = self.engine.device
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
+        if keep_best is not None:  # behind the sync: the decisions the device has taken so far, read once
+            n_dec = self.engine.best_state()["evals"]
+            del self._best_iters[n_dec:]
+            self._best_iters += [None] * (n_dec - len(self._best_iters))
         if self.schedule is not None:  # behind the sync: the device's update count, read once
             self._fill_window(epochs * len(plan.steps))
             self._win_left = 1 << 62  # (step() inside this call leaves the window alone)
@@ -1068,6 +1126,8 @@ class DataParallelTrainer:
                 slot = eval_slot(epoch)
                 if slot >= 0:  # behind the epoch's plan, ahead of the epoch's sync (if any)
                     self.engine.enqueue_eval(slot)
+                    if keep_best is not None:
+                        self._enqueue_keep_best(slot)
                 if xgmi_live or ag_live:
                     self.assert_comm_ok()  # syncs; every rank raises together
                 self.iter += len(plan.steps)
@@ -1075,6 +1135,8 @@ class DataParallelTrainer:
                 stats.images += sum((ln // self.R) * self.R for _, ln in plan.steps)
                 if slot >= 0:
                     eval_enqueued(slot, epoch)
+                    if keep_best is not None:
+                        best_enqueued(epoch)
                 if on_event is not None:
                     if dev.type == "cuda":
                         torch.cuda.synchronize(dev)
@@ -1113,13 +1175,19 @@ class DataParallelTrainer:
             slot = eval_slot(epoch)
             if slot >= 0:
                 self.engine.enqueue_eval(slot)
+                if keep_best is not None:
+                    self._enqueue_keep_best(slot)
             if xgmi_live or ag_live:
                 self.assert_comm_ok()
             if slot >= 0:
                 eval_enqueued(slot, epoch)
+                if keep_best is not None:
+                    best_enqueued(epoch)
 
         try:
             for epoch in range(epochs):
+                if stop_seen[0]:  # the device's rule stopped at an evaluation the host has looked at
+                    break
                 # the recovery point: parameters (+ derived planes) and the step counter at the epoch start
                 can_recover = (self.recover and self.recovered is None and (xgmi_live or ag_live))
                 snap = (self._snapshot(), self.iter, stats.steps, stats.images, len(stats.losses)) \
@@ -1140,12 +1208,23 @@ class DataParallelTrainer:
                 # the xGMI hand-off's ordering rests on write-through stores (csrc/comm/xgmi_allreduce.hip):
                 # a stale peer read would leave the replicas different -- checked bitwise once per train()
                 raise CommFailure(f"rank {self.rank}: replicas differ after xGMI data-parallel training")
-            if n_ev:  # the slots not read yet: one copy, one all-reduce
-                if len(ev_read) < n_ev:
+            if n_ev:  # the slots not read yet: one copy, one all-reduce (an early return leaves the later slots unused)
+                done = sorted(ev_meta)
+                if len(ev_read) < len(done):
                     recs = self._read_evals(n_ev)
-                    for s_ in range(n_ev):
+                    for s_ in done:
                         ev_read.setdefault(s_, recs[s_])
-                stats.evals = [{"epoch": ev_meta[s_][0], "iter": ev_meta[s_][1], **ev_read[s_]} for s_ in range(n_ev)]
+                stats.evals = [{"epoch": ev_meta[s_][0], "iter": ev_meta[s_][1], **ev_read[s_]} for s_ in done]
+            if keep_best is not None:
+                st = self.engine.best_state()
+                stats.stopped, stats.stop_index = st["stopped"], st["stop_index"]
+                i = st["best_index"]
+                if i >= 0:
+                    ep = best_epochs.get(i)
+                    ev = next((r for r in stats.evals if r["epoch"] == ep), None) if ep is not None else None
+                    stats.best = {"index": i, "iter": self._best_iters[i] if i < len(self._best_iters) else None,
+                                  "epoch": ep, "metric": st["best_metric"], "monitor": st["monitor"],
+                                  "loss": ev["loss"] if ev else None, "accuracy": ev["accuracy"] if ev else None}
             self.comm.barrier()
         finally:
             self._win_left = 0  # (a hand-driven step() after this call refills the window from the device's count)
@@ -1154,6 +1233,62 @@ class DataParallelTrainer:
         stats.seconds = time.perf_counter() - t0
         self.sync_to(self.nn)
         return stats
+
+    # ------------------------------------------------------- keep the best weights
+    def _enqueue_keep_best(self, slot: int) -> None:
+        """The decision behind enqueue_eval(slot).  One rank: the launch reads the stats slot itself.  R > 1: pack this
+        rank's triple into its row, SUM all-reduce the [R][3] rows (an exact all-gather: every other rank wrote zeros),
+        decide from the rows -- on-stream for RCCL, through a host copy for host-side communicators, as _read_evals."""
+        e = self.engine
+        if self.R == 1:
+            e.enqueue_keep_best(slot)
+            return
+        from .comm import TorchDistComm
+
+        e.pack_best_rows(slot, self.rank)
+        rows = e.best_rows
+        if self.allreduce_mode == "host":
+            import torch.distributed as dist
+
+            g = rows.cpu()
+            dist.all_reduce(g, group=self._host_group)
+            rows.copy_(g)
+        elif isinstance(self.comm, TorchDistComm) and self.comm.backend != "nccl" and rows.device.type == "cuda":
+            g = rows.cpu()
+            self.comm.allreduce_(g)
+            rows.copy_(g)
+        else:
+            self.comm.allreduce_(rows)
+        e.enqueue_keep_best(slot, rows)
+
+    def enable_keep_best(self, monitor: str = "loss", min_delta: float = 0.0, patience: int | None = None) -> None:
+        """What train(keep_best=...) does on entry; needed by hand only ahead of set_best_state() on a resume."""
+        self.engine.enable_keep_best(monitor, min_delta, patience, ranks=self.R)
+
+    def best_state(self) -> dict:
+        """The device's record (engine.best_state()) plus ``iter``: the iteration counter behind the best evaluation
+        (None when unknown).  Synchronises."""
+        st = self.engine.best_state()
+        i = st["best_index"]
+        st["iter"] = self._best_iters[i] if 0 <= i < len(self._best_iters) else None
+        return st
+
+    def restore_best(self) -> dict:
+        """Make the best weights the current ones (a device copy, then ``nn``): what train() never does by itself.
+        The iteration counter and the optimizer state stay those of the last epoch run.  Returns the record."""
+        self.engine.restore_best()
+        self.sync_to(self.nn)
+        return self.best_state()
+
+    def reset_best(self) -> None:
+        self.engine.reset_best()
+        self._best_iters = []
+
+    def set_best_state(self, record, params=None, iters=None) -> None:
+        """Resume: the record and best weights of a checkpoint (engine.set_best_state; enable_keep_best() first) and
+        the iteration counters behind the decisions taken so far, where known."""
+        self.engine.set_best_state(record, params)
+        self._best_iters = list(iters) if iters is not None else []
 
     def sync_to(self, nn) -> None:
         W1, b1, W2, b2 = self.engine.get_params()

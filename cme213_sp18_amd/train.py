@@ -63,7 +63,8 @@ def run(cfg: TrainConfig) -> dict:
     from .optim import Optimizer
     from .parallel.launcher import PlacementError, init_distributed, shutdown, verify_placement
     from .parallel.trainer import DataParallelTrainer
-    from .utils.checkpoint import checkNNErrors, load_checkpoint, load_optim_state, save_checkpoint
+    from .utils.checkpoint import (checkNNErrors, load_best_state, load_checkpoint, load_optim_state,
+                                   save_checkpoint)
     from .utils.common import precision, save_label
     from .utils.data import load_dataset
 
@@ -104,6 +105,9 @@ def run(cfg: TrainConfig) -> dict:
         policy = sched is not None or clip is not None  # (plain SGD then keeps an update count too: optim_t)
         keeps_state = opt.stateful or policy
         opt_state = None  # the checkpoint's optimizer state (both runs continue it)
+        best_rule = ({"monitor": cfg.keep_best, "min_delta": float(cfg.min_delta), "patience": cfg.patience}
+                     if cfg.keep_best else None)
+        best_saved = None  # the checkpoint's keep-best state (continued when the flags agree)
         if cfg.resume:
             nn, meta = load_checkpoint(cfg.resume)
             log0(rank, f"Resumed from {cfg.resume}: {meta}")
@@ -122,6 +126,14 @@ def run(cfg: TrainConfig) -> dict:
                            "optimizer state starts fresh")
             elif opt.stateful and opt_state is None:
                 log0(rank, "warning: the checkpoint holds no optimizer state (optim.npz): it starts fresh")
+            saved_best = load_best_state(cfg.resume, meta)
+            saved_rule = ({k: saved_best[k] for k in ("monitor", "min_delta", "patience")}
+                          if saved_best is not None else None)
+            if saved_rule != best_rule:
+                log0(rank, f"warning: the checkpoint was trained with keep-best {saved_rule}, this run uses "
+                           f"{best_rule}: the best weights and the patience count do not continue the checkpoint's")
+            elif saved_best is not None:
+                best_saved = saved_best
             if meta.get("shuffle_seed") != cfg.shuffle_seed:
                 log0(rank, f"warning: the checkpoint was trained with --shuffle-seed {meta.get('shuffle_seed')}, this "
                            f"run uses {cfg.shuffle_seed}: the epochs' orders do not continue the checkpoint's")
@@ -171,6 +183,12 @@ def run(cfg: TrainConfig) -> dict:
         if eval_every > 0:
             tr.load_eval(ds.x_dev, ds.y_dev)
         train_kw = {"eval_every": eval_every} if eval_every > 0 else {}
+        if cfg.keep_best:
+            train_kw.update(keep_best=cfg.keep_best, patience=cfg.patience, min_delta=cfg.min_delta,
+                            stop_check_every=cfg.stop_check_every)
+            if best_saved is not None:
+                tr.enable_keep_best(cfg.keep_best, cfg.min_delta, cfg.patience)
+                tr.set_best_state(best_saved["record"], best_saved["params"], best_saved.get("iters"))
         # a resumed run continues the iteration counter (loss lines, -d diff rows and the print_flag
         # schedule pick up where the checkpoint left off; CpuGpuDiff.txt is appended to, not truncated)
         tr.iter = int(meta.get("iter", 0))
@@ -184,6 +202,12 @@ def run(cfg: TrainConfig) -> dict:
                                   **({"schedule": sched.as_meta()} if sched is not None else {}),
                                   **({"clip_norm": clip} if clip is not None else {})}
         ckpt_optim = lambda: tr.engine.optim_state() if keeps_state else None  # noqa: E731
+
+        def ckpt_best():
+            if not cfg.keep_best:
+                return None
+            return {**best_rule, "record": tr.engine.best_records()[0].tolist(), "iter": tr.best_state()["iter"],
+                    "iters": list(tr._best_iters), "params": tr.engine.best_params()}
         seg = cfg.ckpt_every if (cfg.ckpt_every > 0 and cfg.ckpt_dir) else cfg.num_epochs
         done, st = 0, None
         while done < cfg.num_epochs or st is None:  # train in checkpoint segments
@@ -197,16 +221,39 @@ def run(cfg: TrainConfig) -> dict:
                 st.images += s1.images
                 st.losses += s1.losses
                 st.evals += s1.evals
+                st.best, st.stopped, st.stop_index = s1.best, s1.stopped, s1.stop_index
             done += k
+            if cfg.keep_best and s1.stopped:  # the device's rule stopped and the host has seen it
+                done += s1.steps // max(1, tr.steps_per_epoch()) - k  # (the epochs this segment really ran)
+                break
             if cfg.ckpt_dir and done < cfg.num_epochs:
                 if rank == 0:
-                    save_checkpoint(nn, cfg.ckpt_dir, meta=ckpt_meta(done), optim_state=ckpt_optim())
+                    save_checkpoint(nn, cfg.ckpt_dir, meta=ckpt_meta(done), optim_state=ckpt_optim(),
+                                    best=ckpt_best())
                     jlog({"event": "checkpoint", "dir": cfg.ckpt_dir, "epochs": done})
                 comm.barrier()
             if k == 0:
                 break
         out.update(par_seconds=st.seconds, images_per_sec=st.images_per_sec, engine_path=tr.engine.path,
                    allreduce=tr.allreduce_impl)
+        if cfg.keep_best:
+            epochs_run = st.steps // max(1, tr.steps_per_epoch())
+            bs = tr.best_state()
+            if bs["stopped"]:
+                log0(rank, f"Early stop: evaluation {bs['stop_index']} was non-improving number "
+                           f"{bs['patience'] + 1} in a row; {epochs_run} epoch(s) run in this call")
+                jlog({"event": "early_stop", "stop_index": bs["stop_index"], "patience": bs["patience"],
+                      "epochs_run": epochs_run, "iter": tr.iter})
+            if cfg.restore_best and bs["best_index"] >= 0:
+                tr.restore_best()  # every rank: before the precision, the predictions and the final checkpoint
+            log0(rank, f"Best evaluation: index {bs['best_index']} (iteration {bs['iter']}), {bs['monitor']} = "
+                       f"{bs['best_metric']:.10g}" + (" -- restored" if cfg.restore_best and bs['best_index'] >= 0
+                                                     else ""))
+            jlog({"event": "best", "index": bs["best_index"], "iter": bs["iter"], "metric": bs["best_metric"],
+                  "monitor": bs["monitor"], "evals": bs["evals"], "stopped": bs["stopped"],
+                  "restored": bool(cfg.restore_best and bs["best_index"] >= 0),
+                  **({k: st.best[k] for k in ("epoch", "loss", "accuracy")} if st.best else {})})
+            out.update(best_index=bs["best_index"], best_metric=bs["best_metric"], stopped=bs["stopped"])
         if tr.profiler is not None:
             phases = tr.profiler.summary()
             out["profile"] = phases
@@ -225,7 +272,7 @@ def run(cfg: TrainConfig) -> dict:
             if ds.y_test is not None:
                 out["par_test_precision"] = precision(pred, ds.y_test)
             if cfg.ckpt_dir:
-                save_checkpoint(nn, cfg.ckpt_dir, meta=ckpt_meta(cfg.num_epochs), optim_state=ckpt_optim())
+                save_checkpoint(nn, cfg.ckpt_dir, meta=ckpt_meta(done), optim_state=ckpt_optim(), best=ckpt_best())
             if (cfg.grade or cfg.debug) and cfg.run_seq:
                 log0(rank, "\nGrading mode on. Checking for correctness")
                 out["correct"] = checkNNErrors(seq_nn, nn, os.path.join(cfg.outdir, "NNErrors.txt"))

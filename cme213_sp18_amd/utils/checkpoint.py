@@ -128,12 +128,17 @@ def checkNNErrors(seq_nn, par_nn, path: str = "Outputs/NNErrors.txt", verbose: b
 
 
 def save_checkpoint(nn, directory: str, meta: dict | None = None, precision: int = 17,
-                    binary: bool = True, optim_state: dict | None = None) -> None:
+                    binary: bool = True, optim_state: dict | None = None, best: dict | None = None) -> None:
     """Resume checkpoint: W0/W1/b0/b1 raw_ascii (exact fp64 by default) + JSON sidecar (+ .npz).
 
     ``optim_state`` (MlpEngine.optim_state(); None for plain SGD): the optimizer's state buffers go to ``optim.npz``
     (fp64, [W1|b1|W2|b2] unpadded, with the running products b1^t, b2^t) and the sidecar records ``optim_kind`` and the
-    update count ``optim_t``; a stale optim.npz of an earlier run is removed otherwise."""
+    update count ``optim_t``; a stale optim.npz of an earlier run is removed otherwise.
+
+    ``best`` (train --keep-best; None otherwise): dict(monitor, min_delta, patience, record = the 8 doubles of the
+    device's record, iter, iters = the iteration counter behind every decision, params = (W1, b1, W2, b2) of the best
+    weights or None before any).  The weights go to ``best/{W0,W1,b0,b1}.mat`` as raw_ascii (exact fp64) and the rest
+    to the sidecar's ``best`` (a NaN metric is written as null)."""
     os.makedirs(directory, exist_ok=True)
     for name, m in zip(_NAMES, _mats(nn)):
         save_raw_ascii(os.path.join(directory, f"{name}.mat"), m, precision)
@@ -147,9 +152,35 @@ def save_checkpoint(nn, directory: str, meta: dict | None = None, precision: int
         m["optim_kind"], m["optim_t"] = optim_state["kind"], int(optim_state["t"])
     elif os.path.exists(onpz):
         os.remove(onpz)
+    if best is not None:
+        rec = [float(v) for v in best["record"]]
+        m["best"] = {"monitor": best["monitor"], "min_delta": float(best["min_delta"]), "patience": best["patience"],
+                     "record": [None if v != v else v for v in rec], "iter": best.get("iter"),
+                     "iters": list(best.get("iters") or [])}
+        if best.get("params") is not None:
+            bd = os.path.join(directory, "best")
+            os.makedirs(bd, exist_ok=True)
+            W1, b1, W2, b2 = best["params"]
+            for name, a in zip(_NAMES, (W1, W2, np.reshape(b1, (-1, 1)), np.reshape(b2, (-1, 1)))):
+                save_raw_ascii(os.path.join(bd, f"{name}.mat"), a, 17)
     m["H"] = list(nn.H)
     with open(os.path.join(directory, "meta.json"), "w") as f:
         json.dump(m, f, indent=1, sort_keys=True)
+
+
+def load_best_state(directory: str, meta: dict) -> dict | None:
+    """The keep-best state a checkpoint holds (the ``best`` dict of save_checkpoint), or None."""
+    b = meta.get("best")
+    if not b:
+        return None
+    out = dict(b)
+    out["record"] = [float("nan") if v is None else float(v) for v in b["record"]]
+    out["params"] = None
+    bd = os.path.join(directory, "best")
+    if out["record"][1] >= 0:
+        W0, W1, b0, b1 = (load_raw_ascii(os.path.join(bd, f"{n}.mat")) for n in _NAMES)
+        out["params"] = (W0, b0.ravel(), W1, b1.ravel())
+    return out
 
 
 def load_optim_state(directory: str, meta: dict) -> dict | None:

@@ -10,6 +10,7 @@
 #include "cpu/io.h"
 #include "cpu/mlp_cpu.h"
 #include "cpu/suite_cpu.h"
+#include "mlp/best.h"
 #include "mlp/clip.h"
 #include "mlp/shuffle.h"
 
@@ -332,6 +333,34 @@ PYBIND11_MODULE(_cpu, m) {
         return cme::window_rate(lr, w.data(), (int)factors.size(), (double)t);
       },
       py::arg("lr"), py::arg("t0"), py::arg("factors"), py::arg("t"));
+
+  // keeping the best validation weights (csrc/mlp/best.h, the header the kernel compiles): one decision.  record = the
+  // 8 doubles {evals, best_index, best_metric, bad, stopped, stop_index, last_metric, spare}; monitor 0 = loss, 1 =
+  // accuracy; patience < 0 never stops; triples = [R][3] doubles {n, correct, loss_sum}, summed in rank order.
+  // Returns (the advanced record, improved).
+  m.def(
+      "best_decide",
+      [](f64arr record, int monitor, double min_delta, int patience, f64arr triples) {
+        if (record.size() != cme::kBestRecWords) throw std::invalid_argument("best_decide: a record of 8 doubles");
+        if (monitor != cme::kBestLoss && monitor != cme::kBestAccuracy)
+          throw std::invalid_argument("best_decide: monitor 0 (loss) or 1 (accuracy)");
+        if (!(min_delta >= 0.0)) throw std::invalid_argument("best_decide: min_delta must be >= 0");
+        if (triples.ndim() != 2 || triples.shape(0) < 1 || triples.shape(1) != 3)
+          throw std::invalid_argument("best_decide: triples [R][3], R >= 1");
+        cme::BestRecord rec = cme::best_load(record.data());
+        const cme::BestRule rule{monitor, min_delta, patience};
+        const double metric = cme::best_metric_of(triples.data(), (int)triples.shape(0), monitor);
+        const bool improved = cme::best_decide(rec, rule, metric);
+        py::array_t<double> out(cme::kBestRecWords);
+        cme::best_store(out.mutable_data(), rec);
+        return py::make_tuple(out, improved);
+      },
+      py::arg("record"), py::arg("monitor"), py::arg("min_delta"), py::arg("patience"), py::arg("triples"));
+  m.def("best_start", [] {
+    py::array_t<double> out(cme::kBestRecWords);
+    cme::best_store(out.mutable_data(), cme::best_start());
+    return out;
+  });
 
   // the per-epoch shuffle's order (csrc/mlp/shuffle.h, the header the gather kernel compiles): sample i of the
   // shuffled set is source sample perm[i]; key = the iteration counter at the epoch start

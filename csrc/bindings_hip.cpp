@@ -14,6 +14,7 @@
 #include "mlp/mlp_kernels.h"
 #include "mlp/mlp_split.h"
 #include "mlp/mlp_step.h"
+#include "mlp/best.h"
 #include "mlp/clip.h"
 #include "mlp/optim.h"
 #include "mlp/shuffle.h"
@@ -359,6 +360,28 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       },
       py::arg("dt"), py::arg("grads"), py::arg("arena"), py::arg("segments"), py::arg("partials"), py::arg("npart"),
       py::arg("stream") = 0);
+  // keeping the best validation weights (csrc/mlp/best.h): one launch behind an evaluation; rec = best_grid(count)
+  // records of 8 doubles; exactly one of slot (a stats slot of eval.h) and rows ([R][3] doubles) is non-zero
+  m.def("best_grid", &cme::best_grid, py::arg("count"));
+  m.def(
+      "mlp_keep_best",
+      [](int dt, int monitor, double min_delta, int patience, uintptr_t params, uintptr_t best, int64_t count,
+         uintptr_t rec, int nrec, uintptr_t slot, uintptr_t rows, int R, uintptr_t s) {
+        cme::BestArgs a;
+        a.dtype = dt; a.rule.monitor = monitor; a.rule.min_delta = min_delta; a.rule.patience = patience;
+        a.params = P<const void>(params); a.best = P<void>(best); a.count = count; a.rec = P<double>(rec);
+        a.nrec = nrec; a.slot = P<const unsigned long long>(slot); a.rows = P<const double>(rows); a.R = R;
+        cme::mlp_keep_best(a, P<void>(s));
+      },
+      py::arg("dt"), py::arg("monitor"), py::arg("min_delta"), py::arg("patience"), py::arg("params"), py::arg("best"),
+      py::arg("count"), py::arg("rec"), py::arg("nrec"), py::arg("slot") = 0, py::arg("rows") = 0, py::arg("R") = 1,
+      py::arg("stream") = 0);
+  m.def(
+      "mlp_best_pack",
+      [](uintptr_t slot, uintptr_t rows, int R, int rank, uintptr_t s) {
+        cme::mlp_best_pack(P<const unsigned long long>(slot), P<double>(rows), R, rank, P<void>(s));
+      },
+      py::arg("slot"), py::arg("rows"), py::arg("R"), py::arg("rank"), py::arg("stream") = 0);
 
   bind_suite(m);
   bind_comm(m);
