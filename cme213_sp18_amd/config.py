@@ -50,6 +50,10 @@ class TrainConfig:
     num_classes: int = 10       # --classes: output classes (up to 64); labels must lie in [0, classes)
     eval_every: int = 0         # --eval-every N: evaluate the resident dev split on the device every N epochs (dp)
     shuffle_seed: int | None = None  # --shuffle-seed S: reshuffle the resident training set on the device every epoch
+    augment_shift: int | None = None    # --augment-shift M: move every training image by up to M pixels per epoch
+    augment_shift_y: int | None = None  # --augment-shift-y: the vertical bound (default: M)
+    augment_seed: int = 0       # --augment-seed S
+    image_shape: str = ""       # --image-shape HxW: the images' rows x columns (default: 28x28, the square of 784)
     gpus: int = 0               # ranks (one per GPU); 0 = WORLD_SIZE of the launcher, else 1.  N > 1 without a
                                 # launcher: the CLI starts the N ranks itself (parallel/launcher.self_launch)
     optimizer: str = "sgd"      # --optimizer sgd | momentum | adam (optim.Optimizer; sequential and parallel run alike)
@@ -87,6 +91,18 @@ class TrainConfig:
                         end_factor=self.lr_end_factor, min_factor=self.lr_min_factor)
 
     @property
+    def augment(self):
+        """The augment.Shift of the --augment-* flags, or None."""
+        from .augment import Shift
+
+        if self.augment_shift is None:
+            return None
+        h, w = parse_image_shape(self.image_shape) if self.image_shape else (None, None)
+        aug = Shift(self.augment_shift, self.augment_shift_y, h, w, self.augment_seed)
+        aug.shape(self.H[0])
+        return aug
+
+    @property
     def optim(self):
         from .optim import Optimizer
 
@@ -96,6 +112,14 @@ class TrainConfig:
     @property
     def H(self):
         return [784, self.num_neuron, self.num_classes]
+
+
+def parse_image_shape(spec: str) -> tuple[int, int]:
+    """'HxW' -> (H, W), both >= 1."""
+    parts = spec.lower().split("x")
+    if len(parts) != 2 or not all(p.isdigit() for p in parts) or int(parts[0]) < 1 or int(parts[1]) < 1:
+        raise ValueError(f"--image-shape must be HxW with positive integers (got {spec!r})")
+    return int(parts[0]), int(parts[1])
 
 
 # fpcode/main.cpp:113-152 -- "DO NOT change the following parameters"
@@ -168,6 +192,14 @@ def build_parser() -> argparse.ArgumentParser:
                     help="reshuffle the resident training set on the device before every epoch (sequential and "
                          "parallel run alike; the order depends on the seed and the iteration counter only, so "
                          "--resume continues the sequence); default: the loaded order every epoch")
+    ap.add_argument("--augment-shift", type=int,
+                    help="before every epoch move each training image by its own random (dx, dy), |dx| and |dy| <= M, "
+                         "on the device (zeros move in; sequential and parallel run alike; the shifts depend on the "
+                         "seed, the iteration counter and the sample only, so --resume continues the sequence); "
+                         "default: no augmentation")
+    ap.add_argument("--augment-shift-y", type=int, help="the vertical bound of --augment-shift (default: M)")
+    ap.add_argument("--augment-seed", type=int, help="seed of the shifts (default 0)")
+    ap.add_argument("--image-shape", help="HxW: rows x columns of the images, H * W = 784 (default 28x28)")
     ap.add_argument("--optimizer", choices=["sgd", "momentum", "adam"],
                     help="the update rule (default sgd, the reference's w -= lr g); momentum and adam keep their state "
                          "on the device and cost one extra launch per step (data parallel only)")
@@ -257,7 +289,10 @@ def parse_config(argv=None) -> TrainConfig:
     if cfg.keep_best and ((cfg.patience is not None and cfg.patience < 0) or cfg.min_delta < 0
                           or cfg.stop_check_every < 0):
         ap.error("--patience, --min-delta and --stop-check-every must be >= 0")
+    if cfg.augment_shift is None and any(k in explicit for k in ("augment_shift_y", "augment_seed", "image_shape")):
+        ap.error("--augment-shift-y, --augment-seed and --image-shape need --augment-shift")
     try:
+        cfg.augment  # the image shape and the bounds (augment.Shift validates)
         cfg.optim  # the hyper-parameters' ranges (optim.Optimizer validates)
         cfg.schedule
         from .optim import resolve_policy

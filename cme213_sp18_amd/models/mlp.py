@@ -109,7 +109,7 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
           batch_size: int = 800, grad_check: bool = False, print_every: int = -1, debug: bool = False,
           outdir: str = "Outputs", shift: bool = True, ckpt_precision: int = 12, iter0: int = 0,
           shuffle_seed: int | None = None, optimizer=None, optim_state: dict | None = None, schedule=None,
-          clip_norm: float | None = None, update_log: list | None = None) -> list[float]:
+          clip_norm: float | None = None, update_log: list | None = None, augment=None) -> list[float]:
     """Sequential fp64 minibatch SGD on the CPU -- the oracle (neural_network.cpp:219-279).
 
     ``optimizer``: an ``optim.Optimizer`` (None or ``Optimizer.sgd()``: the reference's plain update).  A stateful
@@ -131,6 +131,10 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
     epoch at a time on ``X[perm_e]``, perm_e = epoch_permutation(N, seed, iteration counter at the epoch start) -- the
     one implementation in csrc/mlp/shuffle.h -- with the counter carried, so the oracle stays comparable with a
     shuffled parallel run.
+
+    ``augment`` (an ``augment.Shift``; the parallel trainers' ``augment=``): one native epoch at a time on
+    ``apply_shifts(X[perm_e], shifts_e[perm_e], h, w)``, shifts_e = the keyed shifts of the loaded samples in the epoch
+    that starts at that iteration counter (csrc/mlp/augment.h); without ``shuffle_seed`` the order is the loaded one.
 
     ``grad_check`` runs a numerical gradient check on the first batch (the
     reference's threshold of 1000 made it a no-op; we assert a real bound).
@@ -173,7 +177,7 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
     elif update_log is not None:
         raise ValueError("update_log needs a schedule, clip_norm or a stateful optimizer")
     try:
-        if shuffle_seed is None:
+        if shuffle_seed is None and augment is None:
             if rates is not None:
                 kw["rates"] = rates
             return list(cpu().train(*nn.params, X, labels, float(learning_rate), float(reg), int(epochs),
@@ -181,11 +185,19 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
                                     int(ckpt_precision), int(iter0), **kw))
         losses: list[float] = []
         it = int(iter0)
+        if augment is not None:
+            from ..augment import apply_shifts, epoch_shifts
+
+            img_h, img_w = augment.shape(X.shape[1])
         for ep in range(int(epochs)):
-            perm = cpu().epoch_permutation(n, int(shuffle_seed), it)
+            perm = (cpu().epoch_permutation(n, int(shuffle_seed), it) if shuffle_seed is not None
+                    else np.arange(n, dtype=np.int32))
             if rates is not None:
                 kw["rates"] = np.ascontiguousarray(rates[ep * nb:(ep + 1) * nb])
-            losses += cpu().train(*nn.params, np.ascontiguousarray(X[perm]), np.ascontiguousarray(labels[perm]),
+            Xe = np.ascontiguousarray(X[perm])
+            if augment is not None:
+                Xe = apply_shifts(Xe, epoch_shifts(n, augment, it)[perm], img_h, img_w)
+            losses += cpu().train(*nn.params, Xe, np.ascontiguousarray(labels[perm]),
                                   float(learning_rate), float(reg), 1, int(batch_size), int(print_every),
                                   bool(debug), outdir, shift, int(ckpt_precision), it, **kw)
             it += nb

@@ -146,6 +146,10 @@ class MlpEngine:
         # the pristine rows as loaded (load_dataset(keep_source=True)): what enqueue_shuffle gathers from
         self.X0 = self.labels0 = self._perm = None
         self.shuffle_launches = 0  # shuffle kernel launches enqueued (0: the kernel was never loaded)
+        # the augmenting gather (enqueue_augment): its launches, and the (dx, dy) of every resident sample -- allocated
+        # by the first augmentation, so a run without one holds nothing
+        self.augment_launches = 0
+        self._shifts = None
         self._eval = None  # the resident validation set and its evaluation buffers (load_eval)
         self._normalize = False
         self.xscale = 1.0
@@ -301,7 +305,7 @@ class MlpEngine:
             self.XTw = self.XT.to(torch.bfloat16).contiguous()
         self.labels = torch.as_tensor(np.asarray(labels, dtype=np.int32)).to(self.device).contiguous()
         self.num_samples = int(self.X.shape[0])
-        self.X0 = self.labels0 = self._perm = None
+        self.X0 = self.labels0 = self._perm = self._shifts = None
         if keep_source:
             # the loaded tensors become the (never written) source and the step reads fresh copies: on the CPU the
             # loaded ones may share memory with the caller's arrays, which a shuffle must not rewrite
@@ -323,8 +327,71 @@ class MlpEngine:
         self._shuffle(int(seed), int(key), False)
 
     def unshuffle(self) -> None:
-        """The order of load_dataset() again."""
+        """The order of load_dataset() again -- and, after an augmentation, its pixels: shifts() is zero again."""
         self._shuffle(0, 0, True)
+
+    # ------------------------------------------------ per-epoch augmentation
+    def enqueue_augment(self, aug, key: int, shuffle_seed: int | None = None) -> None:
+        """enqueue_shuffle with the images moved on the way (augment.Shift; csrc/mlp/augment.h): every resident layout
+        is rewritten in place from the pristine rows so that sample i is SOURCE sample perm[i] -- perm =
+        epoch_permutation(N, shuffle_seed, key), or the loaded order without a seed -- shifted by
+        epoch_shifts(N, aug.seed, key, ...)[perm[i]].  The shift belongs to the source sample, so the order does not
+        change it.  Never composed with the previous state.  On the hip backend one launch of the augmenting gather
+        (csrc/mlp/augment.hip) on the current stream: no sync, no read-back, and the buffers keep their addresses."""
+        if self.X is None:
+            raise RuntimeError("load_dataset() first")
+        if self.X0 is None:
+            raise RuntimeError("no pristine copy of the training set: load_dataset(..., keep_source=True) first")
+        key, seed = int(key), 0 if shuffle_seed is None else int(shuffle_seed)
+        if not (0 <= seed < 1 << 32 and 0 <= key < 1 << 32):
+            raise ValueError("shuffle seed and key must be in [0, 2^32)")
+        N, P = self.num_samples, self.P
+        h, w = aug.shape(P)
+        if N == 0:
+            return
+        if self._shifts is None:
+            self._shifts = torch.zeros(N, 2, dtype=torch.int32, device=self.device)
+        if self.backend == "hip":
+            ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
+            hip().mlp_augment(ptr(self.X0), ptr(self.labels0), ptr(self.X), ptr(self.labels), ptr(self.XT),
+                              ptr(self.Xs), ptr(self.Xw), ptr(self.XTw), ptr(self._perm), ptr(self._shifts), N, P,
+                              self.X.element_size(), h, w, aug.max_dx, aug.max_dy, aug.seed, key,
+                              int(shuffle_seed is not None), seed,
+                              torch.cuda.current_stream(self.device).cuda_stream)
+            self.augment_launches += 1
+            return
+        with torch.no_grad():
+            perm = (np.arange(N, dtype=np.int32) if shuffle_seed is None else cpu().epoch_permutation(N, seed, key))
+            shifts = cpu().epoch_shifts(N, aug.seed, key, aug.max_dx, aug.max_dy)[perm]
+            self._perm.copy_(torch.from_numpy(perm))
+            self._shifts.copy_(torch.from_numpy(shifts))
+            # the rule moves bytes (zero fill = all-zero bits): the rows go through the host as same-size integers
+            bits = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[self.X0.element_size()]
+            rows = self.X0.index_select(0, self._perm.long()).view(bits).cpu().numpy()
+            moved = torch.from_numpy(cpu().augment_rows(rows, shifts, h, w)).view(self.X.dtype)
+            self.X.copy_(moved)
+            self.labels.copy_(self.labels0.index_select(0, self._perm.long()))
+            self._rebuild_from_rows()
+
+    def shifts(self) -> torch.Tensor:
+        """The current augmentation as a device int32 [N][2]: resident sample i is its source image moved by
+        (dx, dy) = shifts()[i] (zeros before any augmentation, and after unshuffle() or a plain shuffle)."""
+        if self._shifts is not None:
+            return self._shifts
+        if self.X is None:
+            raise RuntimeError("load_dataset() first")
+        return torch.zeros(self.num_samples, 2, dtype=torch.int32, device=self.device)
+
+    def _rebuild_from_rows(self) -> None:
+        """XT, Xs, Xw, XTw again from X (torch backend)."""
+        P = self.P
+        if self.XT is not None:
+            self.XT[:P].copy_(self.X.t())
+        if self.Xs is not None:
+            self.Xs.copy_(fragment_order_pixels(self.X))
+        if self.Xw is not None:
+            self.Xw.copy_(self.X.to(torch.bfloat16))
+            self.XTw[:P].copy_(self.X.t().to(torch.bfloat16))
 
     def permutation(self) -> torch.Tensor:
         """The current order as a device int32 tensor: resident sample i is loaded sample permutation()[i] (the
@@ -345,6 +412,8 @@ class MlpEngine:
         N, P = self.num_samples, self.P
         if N == 0:
             return
+        if self._shifts is not None:  # (only after an augmentation: the plain gather restores the loaded pixels)
+            self._shifts.zero_()
         if self.backend == "hip":
             ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
             hip().mlp_shuffle(ptr(self.X0), ptr(self.labels0), ptr(self.X), ptr(self.labels), ptr(self.XT),
@@ -359,13 +428,7 @@ class MlpEngine:
             idx = self._perm.long()
             self.X.copy_(self.X0.index_select(0, idx))
             self.labels.copy_(self.labels0.index_select(0, idx))
-            if self.XT is not None:
-                self.XT[:P].copy_(self.X.t())
-            if self.Xs is not None:
-                self.Xs.copy_(fragment_order_pixels(self.X))
-            if self.Xw is not None:
-                self.Xw.copy_(self.X.to(torch.bfloat16))
-                self.XTw[:P].copy_(self.X.t().to(torch.bfloat16))
+            self._rebuild_from_rows()
 
     def set_params(self, W1, b1, W2, b2):
         self.join()

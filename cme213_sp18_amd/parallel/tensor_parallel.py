@@ -46,7 +46,7 @@ class TensorParallelTrainer:
     def __init__(self, nn, comm: Communicator | None = None, device=None, dtype: str = "f32",
                  batch_size: int = 800, backend: str = "hip", shift: bool = True, normalize: bool = False,
                  path: str = "auto", allreduce: str = "auto", shuffle_seed: int | None = None, optimizer=None,
-                 schedule=None, clip_norm=None):
+                 schedule=None, clip_norm=None, augment=None):
         from ..optim import resolve
 
         # the shard's update stays inside its weight-gradient launch (plain SGD); the stateful rules are
@@ -59,6 +59,7 @@ class TensorParallelTrainer:
                              "gradient-norm clipping needs data parallelism (--parallel dp)")
         self.nn = nn
         self.shuffle_seed = None if shuffle_seed is None else int(shuffle_seed)  # (DataParallelTrainer's)
+        self.augment = augment  # an augment.Shift or None (DataParallelTrainer's)
         self.comm = comm or NullComm()
         self.R, self.rank = self.comm.world_size, self.comm.rank
         P, H, C = nn.H
@@ -174,8 +175,10 @@ class TensorParallelTrainer:
 
     # -------------------------------------------------------------------- data
     def load(self, x_train, y_train):
+        if self.augment is not None:
+            self.augment.shape(self.engine.P)  # (raises when the image shape or the bounds do not fit)
         self.engine.load_dataset(x_train, y_train, normalize=self.normalize,
-                                 keep_source=self.shuffle_seed is not None)
+                                 keep_source=self.shuffle_seed is not None or self.augment is not None)
         self.N = self.engine.num_samples
 
     def epoch_plan(self, N: int | None = None) -> EpochPlan:
@@ -312,7 +315,8 @@ class TensorParallelTrainer:
         JSON-lines epoch events, ``fault=(rank, step)`` injection); graph-replayed epochs when no loss is
         printed.  ``debug`` (the reference's per-iteration CPU diff) is data-parallel only.  ``shuffle_seed``
         (default: the constructor's): the resident set -- whole on every rank -- is reordered on the device before
-        each epoch, as in DataParallelTrainer.train.  ``keep_best`` (and patience / min_delta / stop_check_every) is
+        each epoch, as in DataParallelTrainer.train -- with the constructor's ``augment`` by the augmenting gather.
+        ``keep_best`` (and patience / min_delta / stop_check_every) is
         refused: it acts on the device-side evaluation, which is data-parallel only."""
         from .trainer import CommFailure, FaultInjected
 
@@ -331,7 +335,9 @@ class TensorParallelTrainer:
         for epoch in range(epochs):
             if fault is not None and fault[0] == self.rank and self.iter <= fault[1] < self.iter + len(plan.steps):
                 raise FaultInjected(f"injected fault on rank {self.rank} at step {fault[1]}")
-            if seed is not None:
+            if self.augment is not None:  # the augmenting gather in the shuffle's place (the same order)
+                self.engine.enqueue_augment(self.augment, self.iter, seed)
+            elif seed is not None:
                 self.engine.enqueue_shuffle(seed, self.iter)
             if print_every <= 0 and self.profiler is None:
                 self.run_plan(plan, lr, reg, use_graphs=self.use_graphs)

@@ -242,7 +242,7 @@ class DataParallelTrainer:
                  normalize: bool = False, path: str = "auto", allreduce: str = "auto", overlap: bool = True,
                  overlap_chunks: int = 0, fuse_allreduce: bool = True, executor: str = "auto",
                  grad_wire: str = "auto", fused_form: str = "auto", shuffle_seed: int | None = None,
-                 optimizer=None, schedule=None, clip_norm=None):
+                 optimizer=None, schedule=None, clip_norm=None, augment=None):
         self.nn = nn
         # the update rule (optim.Optimizer): None / Optimizer.sgd() = the plain-SGD code as it stands.  A stateful
         # rule (momentum, Adam) runs every step in gradient mode followed by engine.apply() -- one extra launch --
@@ -268,6 +268,10 @@ class DataParallelTrainer:
         # launched): load() keeps the pristine rows and train() reorders every layout on the device before each
         # epoch -- the order of the epoch that starts at iteration counter i is epoch_permutation(N, seed, i)
         self.shuffle_seed = None if shuffle_seed is None else int(shuffle_seed)
+        # per-epoch augmentation of the resident training set (an augment.Shift; None: nothing kept, nothing launched):
+        # load() keeps the pristine rows and train() enqueues the augmenting gather INSTEAD of the shuffle before each
+        # epoch -- the order as above (the loaded one without a shuffle seed), every image moved by its own keyed shift
+        self.augment = augment
         # how run_plan enqueues a plan: "auto" = the native C++ step loop (MlpStep.run_steps) for plans of
         # consecutive full batches on the fused paths (pure device work), else the captured HIP graph;
         # "graph" = always the graph; "eager" = Python step by step
@@ -557,8 +561,10 @@ class DataParallelTrainer:
 
     # ---------------------------------------------------------------- data
     def load(self, x_train, y_train):
+        if self.augment is not None:
+            self.augment.shape(self.engine.P)  # (raises when the image shape or the bounds do not fit)
         self.engine.load_dataset(x_train, y_train, normalize=self.normalize,
-                                 keep_source=self.shuffle_seed is not None)
+                                 keep_source=self.shuffle_seed is not None or self.augment is not None)
         self.N = self.engine.num_samples
         self._graphs.clear()
         if self._xgmi_fused is not None:
@@ -1018,6 +1024,13 @@ class DataParallelTrainer:
         forms the same order from the same seed.  The validation set is never shuffled.  Afterwards the set stays in
         the last epoch's order.
 
+        With ``augment`` (the constructor's augment.Shift) the augmenting gather is enqueued in the shuffle's place
+        (engine.enqueue_augment(augment, self.iter, seed), one launch): the same order -- the loaded one without a
+        seed -- with every training image moved by its own shift, keyed by (augment.seed, iteration counter at the
+        epoch start, loaded sample index).  A recovered epoch repeats its shifts, train(2) + train(2) equals train(4),
+        every rank forms the same pixels, and the validation set and predict() are never augmented.  Afterwards the
+        set stays in the last epoch's state (engine.permutation(), engine.shifts()); step(start, ...) indexes it.
+
         With a schedule (the constructor's), the call reads the device's update count once, behind its start-of-call
         sync, and fills the schedule window for ``epochs * steps_per_epoch`` updates from there, steps_per_epoch =
         len(epoch_plan().steps): the apply launch looks its factor up on the device, so every epoch replays from the
@@ -1117,7 +1130,10 @@ class DataParallelTrainer:
                 raise FaultInjected(f"injected fault on rank {self.rank} at step {fault[1]}")
 
         def run_epoch(epoch: int) -> None:
-            if seed is not None:  # (inside run_epoch: a recovered epoch restores self.iter and gets the same order)
+            # (inside run_epoch: a recovered epoch restores self.iter and gets the same order and the same shifts)
+            if self.augment is not None:
+                self.engine.enqueue_augment(self.augment, self.iter, seed)
+            elif seed is not None:
                 self.engine.enqueue_shuffle(seed, self.iter)
             if not host_needed:
                 maybe_fault(self.iter, len(plan.steps))

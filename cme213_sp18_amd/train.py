@@ -81,8 +81,10 @@ def run(cfg: TrainConfig) -> dict:
         raise SystemExit(2)
     jlog = JsonLog(cfg.log_json, rank)
     try:
+        aug = cfg.augment  # an augment.Shift or None
         jlog({"event": "config", "world": world, "device": str(device), **placement, **{
-            k: v for k, v in vars(cfg).items() if isinstance(v, (int, float, str, bool))}})
+            k: v for k, v in vars(cfg).items() if isinstance(v, (int, float, str, bool))},
+            "augment": aug.to_meta() if aug is not None else None})
         log0(rank, f"Number of processes = {world}")
         log0(rank, f"Device = {device} ({torch.cuda.get_device_name(device) if device.type == 'cuda' else 'cpu'})")
         if cfg.grade == 4:
@@ -137,6 +139,12 @@ def run(cfg: TrainConfig) -> dict:
             if meta.get("shuffle_seed") != cfg.shuffle_seed:
                 log0(rank, f"warning: the checkpoint was trained with --shuffle-seed {meta.get('shuffle_seed')}, this "
                            f"run uses {cfg.shuffle_seed}: the epochs' orders do not continue the checkpoint's")
+            from .augment import Shift
+
+            if Shift.from_meta(meta.get("augment")) != aug:
+                log0(rank, f"warning: the checkpoint was trained with augmentation {meta.get('augment')}, this run "
+                           f"uses {aug.to_meta() if aug is not None else None}: the epochs' shifts do not continue "
+                           "the checkpoint's")
         else:
             nn = NeuralNetwork(cfg.H)
         seq_nn = nn.copy()
@@ -149,7 +157,7 @@ def run(cfg: TrainConfig) -> dict:
             mlp.train(seq_nn, xs, ds.y_train, cfg.learning_rate, cfg.reg, cfg.num_epochs, cfg.batch_size,
                       False, cfg.print_every, cfg.debug, cfg.outdir, cfg.softmax_shift, cfg.ckpt_precision,
                       iter0=int(meta.get("iter", 0)), shuffle_seed=cfg.shuffle_seed, optimizer=opt,
-                      optim_state=copy.deepcopy(opt_state), schedule=sched, clip_norm=clip)
+                      optim_state=copy.deepcopy(opt_state), schedule=sched, clip_norm=clip, augment=aug)
             out["seq_seconds"] = time.perf_counter() - t
             log0(rank, f"Time for Sequential Training: {out['seq_seconds']:.6f} seconds")
             out["seq_dev_precision"] = precision(mlp.predict(seq_nn, xd, cfg.softmax_shift), ds.y_dev)
@@ -166,14 +174,14 @@ def run(cfg: TrainConfig) -> dict:
                                        backend=backend, shift=cfg.softmax_shift, normalize=cfg.normalize,
                                        path=cfg.path,
                                        allreduce=tp_allreduce_mode(cfg.allreduce), shuffle_seed=cfg.shuffle_seed,
-                                       optimizer=opt, schedule=sched, clip_norm=clip)
+                                       optimizer=opt, schedule=sched, clip_norm=clip, augment=aug)
             tr.use_graphs = cfg.use_graphs
         else:
             tr = DataParallelTrainer(nn, comm=comm, device=device, dtype=cfg.dtype, batch_size=cfg.batch_size,
                                      backend=backend, shift=cfg.softmax_shift, use_graphs=cfg.use_graphs,
                                      normalize=cfg.normalize, path=cfg.path, allreduce=cfg.allreduce,
                                      overlap_chunks=cfg.overlap_chunks, shuffle_seed=cfg.shuffle_seed, optimizer=opt,
-                                     schedule=sched, clip_norm=clip)
+                                     schedule=sched, clip_norm=clip, augment=aug)
             if opt_state is not None:
                 tr.engine.set_optim_state(opt_state)
         tr.load(ds.x_train, ds.y_train)
@@ -198,6 +206,7 @@ def run(cfg: TrainConfig) -> dict:
         ckpt_meta = lambda done: {"epochs": done + meta.get("epochs", 0), "lr": cfg.learning_rate, "reg": cfg.reg,
                                   "seed": cfg.seed, "dtype": cfg.dtype, "iter": tr.iter,
                                   "shuffle_seed": cfg.shuffle_seed,
+                                  "augment": aug.to_meta() if aug is not None else None,
                                   **({"optimizer": opt.as_meta()} if opt.stateful else {}),
                                   **({"schedule": sched.as_meta()} if sched is not None else {}),
                                   **({"clip_norm": clip} if clip is not None else {})}

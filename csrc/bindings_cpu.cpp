@@ -10,6 +10,7 @@
 #include "cpu/io.h"
 #include "cpu/mlp_cpu.h"
 #include "cpu/suite_cpu.h"
+#include "mlp/augment.h"
 #include "mlp/best.h"
 #include "mlp/clip.h"
 #include "mlp/shuffle.h"
@@ -375,6 +376,56 @@ PYBIND11_MODULE(_cpu, m) {
         return out;
       },
       py::arg("n"), py::arg("seed"), py::arg("key"));
+
+  // the augmentation's shifts (csrc/mlp/augment.h, the header the augmenting gather compiles): row i = (dx, dy) of
+  // SOURCE sample i in the epoch that starts at iteration counter `key`
+  m.def(
+      "epoch_shifts",
+      [](int64_t n, uint32_t seed, uint32_t key, int max_dx, int max_dy) {
+        if (n < 0 || n > INT32_MAX) throw std::invalid_argument("epoch_shifts: n must be in [0, 2^31)");
+        if (max_dx < 0 || max_dy < 0 || max_dx > (1 << 20) || max_dy > (1 << 20))
+          throw std::invalid_argument("epoch_shifts: the shift bounds must be in [0, 2^20]");
+        py::array_t<int32_t> out({n, (int64_t)2});
+        int32_t* o = out.mutable_data();
+        const uint64_t k = cme::augment_key(seed, key);
+        for (int64_t i = 0; i < n; ++i) {
+          const cme::AugmentShift s = cme::augment_shift((uint32_t)i, k, max_dx, max_dy);
+          o[2 * i] = s.dx;
+          o[2 * i + 1] = s.dy;
+        }
+        return out;
+      },
+      py::arg("n"), py::arg("seed"), py::arg("key"), py::arg("max_dx"), py::arg("max_dy"));
+  // rows of h x w images, each moved by its own (dx, dy): out[i][f] = x[i][augment_src_feature(f, ...)] or all-zero
+  // bits.  Any element of 1 / 2 / 4 / 8 bytes (uint8, float32, float64, ...): the rule moves bytes
+  m.def(
+      "augment_rows",
+      [](const py::array& x, const i32arr& shifts, int h, int w) {
+        if (x.ndim() != 2 || !(x.flags() & py::array::c_style))
+          throw std::invalid_argument("augment_rows: x must be a C-contiguous [N][P] array");
+        const int64_t n = x.shape(0), p = x.shape(1), es = x.itemsize();
+        if (es != 1 && es != 2 && es != 4 && es != 8)
+          throw std::invalid_argument("augment_rows: the element size must be 1, 2, 4 or 8 bytes");
+        if (h < 1 || w < 1 || (int64_t)h * w != p) throw std::invalid_argument("augment_rows: h * w must equal P");
+        if (p > INT32_MAX) throw std::invalid_argument("augment_rows: P must be below 2^31");
+        if (shifts.ndim() != 2 || shifts.shape(0) != n || shifts.shape(1) != 2)
+          throw std::invalid_argument("augment_rows: shifts must be int32 [N][2]");
+        py::array out(x.dtype(), {n, p});
+        const char* src = static_cast<const char*>(x.data());
+        char* dst = static_cast<char*>(out.mutable_data());
+        const int32_t* sh = shifts.data();
+        for (int64_t i = 0; i < n; ++i) {
+          const int dx = sh[2 * i], dy = sh[2 * i + 1];
+          for (int64_t f = 0; f < p; ++f) {
+            const int sf = cme::augment_src_feature((int)f, dx, dy, h, w);
+            char* d = dst + (i * p + f) * es;
+            if (sf >= 0) std::memcpy(d, src + (i * p + sf) * es, (size_t)es);
+            else std::memset(d, 0, (size_t)es);
+          }
+        }
+        return out;
+      },
+      py::arg("x"), py::arg("shifts"), py::arg("h"), py::arg("w"));
 
   // ---------------------------------------------------------------- I/O
   m.def(

@@ -17,6 +17,7 @@
 #include "mlp/best.h"
 #include "mlp/clip.h"
 #include "mlp/optim.h"
+#include "mlp/augment.h"
 #include "mlp/shuffle.h"
 #include "suite/suite_kernels.h"
 
@@ -297,6 +298,26 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       py::arg("X0"), py::arg("labels0"), py::arg("X"), py::arg("labels"), py::arg("XT"), py::arg("Xs"), py::arg("Xw"),
       py::arg("XTw"), py::arg("perm"), py::arg("N"), py::arg("P"), py::arg("es"), py::arg("seed"), py::arg("key"),
       py::arg("identity") = 0, py::arg("stream") = 0);
+  // the augmenting gather (csrc/mlp/augment.hip): mlp_shuffle's layouts, each image moved by its keyed (dx, dy);
+  // shuffled != 0: the order of shuffle_key(shuffle_seed, key), else the loaded order
+  m.def(
+      "mlp_augment",
+      [](uintptr_t X0, uintptr_t labels0, uintptr_t X, uintptr_t labels, uintptr_t XT, uintptr_t Xs, uintptr_t Xw,
+         uintptr_t XTw, uintptr_t perm, uintptr_t shifts, int N, int Pd, int es, int h, int w, int max_dx, int max_dy,
+         uint32_t aug_seed, uint32_t key, int shuffled, uint32_t shuffle_seed, uintptr_t s) {
+        cme::AugmentArgs aa;
+        cme::ShuffleArgs& a = aa.base;
+        a.X0 = P<const void>(X0); a.labels0 = P<const int>(labels0); a.X = P<void>(X); a.labels = P<int>(labels);
+        a.XT = P<void>(XT); a.Xs = P<void>(Xs); a.Xw = P<void>(Xw); a.XTw = P<void>(XTw); a.perm = P<int>(perm);
+        a.N = N; a.P = Pd; a.es = es; a.key = cme::shuffle_key(shuffle_seed, key); a.identity = shuffled ? 0 : 1;
+        aa.h = h; aa.w = w; aa.max_dx = max_dx; aa.max_dy = max_dy; aa.akey = cme::augment_key(aug_seed, key);
+        aa.shifts = P<int>(shifts);
+        cme::mlp_augment(aa, P<void>(s));
+      },
+      py::arg("X0"), py::arg("labels0"), py::arg("X"), py::arg("labels"), py::arg("XT"), py::arg("Xs"), py::arg("Xw"),
+      py::arg("XTw"), py::arg("perm"), py::arg("shifts"), py::arg("N"), py::arg("P"), py::arg("es"), py::arg("h"),
+      py::arg("w"), py::arg("max_dx"), py::arg("max_dy"), py::arg("aug_seed"), py::arg("key"),
+      py::arg("shuffled") = 0, py::arg("shuffle_seed") = 0, py::arg("stream") = 0);
   m.def("mlp_split_fused_tiles", &cme::mlp_split_fused_tiles, py::arg("P"), py::arg("H"), py::arg("cap"));
   // the stateful optimizer step (csrc/mlp/optim.h): kind 0 = momentum / Nesterov, 1 = adam; rec = optim_grid(count)
   // records of 4 doubles {t, b1^t, b2^t, 0}
