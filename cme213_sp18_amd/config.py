@@ -77,6 +77,10 @@ class TrainConfig:
     min_delta: float = 0.0      # --min-delta D: an evaluation improves only by more than D
     stop_check_every: int = 0   # --stop-check-every K: the host looks at the stop flag after every K-th evaluated epoch
     restore_best: bool = False  # --restore-best: the best weights become the final ones (outputs and checkpoint)
+    ema: float | None = None    # --ema DECAY: keep an exponential moving average of the weights (csrc/mlp/ema.h; dp)
+    ema_warmup: bool = False    # --ema-warmup: the decay of update t is min(DECAY, (1 + t) / (10 + t))
+    eval_weights: str = ""      # --eval-weights ema | current: the weights --eval-every reads ("": ema when averaging)
+    use_ema: bool = False       # --use-ema: the averaged weights become the final ones (outputs and checkpoint)
 
     @property
     def schedule(self):
@@ -89,6 +93,13 @@ class TrainConfig:
         return Schedule(kind, unit=self.lr_unit, warmup=self.warmup, warmup_start=self.warmup_start,
                         size=self.lr_step_size, gamma=self.lr_gamma, total=self.lr_total,
                         end_factor=self.lr_end_factor, min_factor=self.lr_min_factor)
+
+    @property
+    def ema_rule(self):
+        """The optim.Ema of the --ema flags, or None."""
+        from .optim import Ema
+
+        return Ema(float(self.ema), bool(self.ema_warmup)) if self.ema is not None else None
 
     @property
     def augment(self):
@@ -238,6 +249,19 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--restore-best", action="store_true", default=None,
                     help="after training, make the best weights the current ones: the precision, the predictions and "
                          "the final checkpoint are those of the best evaluation")
+    ap.add_argument("--ema", type=float, metavar="DECAY",
+                    help="keep an exponential moving average of the weights on the device, folded in after every "
+                         "update: e += (1 - DECAY)(p - e), 0 <= DECAY < 1 (torch's get_ema_multi_avg_fn); the "
+                         "sequential run (-s) keeps one too; data parallel only")
+    ap.add_argument("--ema-warmup", action="store_true", default=None,
+                    help="the decay of update t is min(DECAY, (1 + t) / (10 + t)): the early average follows the "
+                         "weights instead of their starting point; needs --ema")
+    ap.add_argument("--eval-weights", choices=["ema", "current"],
+                    help="the weights the --eval-every evaluations (and --keep-best) read: the averaged ones "
+                         "(default with --ema) or the current ones")
+    ap.add_argument("--use-ema", action="store_true", default=None,
+                    help="after training, make the averaged weights the current ones: the precision, the predictions "
+                         "and the final checkpoint are those of the average; needs --ema")
     ap.add_argument("--gpus", type=int,
                     help="number of ranks, one per GPU (the reference's mpirun -np N); started here when no "
                          "launcher started this process")
@@ -289,12 +313,22 @@ def parse_config(argv=None) -> TrainConfig:
     if cfg.keep_best and ((cfg.patience is not None and cfg.patience < 0) or cfg.min_delta < 0
                           or cfg.stop_check_every < 0):
         ap.error("--patience, --min-delta and --stop-check-every must be >= 0")
+    # weight averaging runs over the whole parameter arena of the data-parallel trainer
+    if cfg.ema is not None and cfg.parallel == "tp":
+        ap.error("--ema averages the whole parameter arena, which --parallel tp shards; it needs --parallel dp")
+    ema_flags = [f for f, on in (("--ema-warmup", cfg.ema_warmup), ("--use-ema", cfg.use_ema),
+                                 ("--eval-weights ema", cfg.eval_weights == "ema")) if on]
+    if ema_flags and cfg.ema is None:
+        ap.error(f"{', '.join(ema_flags)} need(s) --ema DECAY")
+    if cfg.use_ema and cfg.restore_best:
+        ap.error("--use-ema and --restore-best both choose the final weights: give one of them")
     if cfg.augment_shift is None and any(k in explicit for k in ("augment_shift_y", "augment_seed", "image_shape")):
         ap.error("--augment-shift-y, --augment-seed and --image-shape need --augment-shift")
     try:
         cfg.augment  # the image shape and the bounds (augment.Shift validates)
         cfg.optim  # the hyper-parameters' ranges (optim.Optimizer validates)
         cfg.schedule
+        cfg.ema_rule  # (optim.Ema validates the decay)
         from .optim import resolve_policy
 
         resolve_policy(None, cfg.clip_norm)

@@ -109,7 +109,8 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
           batch_size: int = 800, grad_check: bool = False, print_every: int = -1, debug: bool = False,
           outdir: str = "Outputs", shift: bool = True, ckpt_precision: int = 12, iter0: int = 0,
           shuffle_seed: int | None = None, optimizer=None, optim_state: dict | None = None, schedule=None,
-          clip_norm: float | None = None, update_log: list | None = None, augment=None) -> list[float]:
+          clip_norm: float | None = None, update_log: list | None = None, augment=None, ema=None,
+          ema_state: dict | None = None) -> list[float]:
     """Sequential fp64 minibatch SGD on the CPU -- the oracle (neural_network.cpp:219-279).
 
     ``optimizer``: an ``optim.Optimizer`` (None or ``Optimizer.sgd()``: the reference's plain update).  A stateful
@@ -135,6 +136,11 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
     ``augment`` (an ``augment.Shift``; the parallel trainers' ``augment=``): one native epoch at a time on
     ``apply_shifts(X[perm_e], shifts_e[perm_e], h, w)``, shifts_e = the keyed shifts of the loaded samples in the epoch
     that starts at that iteration counter (csrc/mlp/augment.h); without ``shuffle_seed`` the order is the loaded one.
+
+    ``ema`` (an ``optim.Ema``; the parallel trainer's ``ema=``): after every update the parameters are folded into an
+    average by the rule of csrc/mlp/ema.h.  ``ema_state`` -- ``optim.new_ema_state(nn)``: {"t": the count of averaged
+    updates, "avg": fp64 over [W1|b1|W2|b2]}, the average starting as a copy of the parameters -- is updated in place
+    and so returned, and a later call continues it; None: a fresh one for this call, dropped afterwards.
 
     ``grad_check`` runs a numerical gradient check on the first batch (the
     reference's threshold of 1000 made it a no-op; we assert a real bound).
@@ -176,6 +182,15 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
             rates = float(learning_rate) * schedule.factors(int(st["t"]), int(epochs) * nb, nb)
     elif update_log is not None:
         raise ValueError("update_log needs a schedule, clip_norm or a stateful optimizer")
+    from ..optim import new_ema_state, resolve_ema
+
+    ema = resolve_ema(ema)
+    if ema is not None:
+        est = ema_state if ema_state is not None else new_ema_state(nn)
+        if est["avg"].size != nn.num_params() or est["avg"].dtype != np.float64:
+            raise ValueError("ema_state does not belong to this network")
+        ema_t = np.array([float(est["t"])], np.float64)
+        kw["ema"] = (float(ema.decay), bool(ema.warmup), est["avg"], ema_t)
     try:
         if shuffle_seed is None and augment is None:
             if rates is not None:
@@ -205,3 +220,5 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
     finally:
         if opt is not None or policy:
             st["t"], st["b1p"], st["b2p"] = int(counter[0]), float(counter[1]), float(counter[2])
+        if ema is not None:
+            est["t"] = int(ema_t[0])

@@ -225,6 +225,50 @@ class _MomentumHelper:
 Optimizer.momentum = _MomentumHelper()
 
 
+@dataclasses.dataclass(frozen=True)
+class Ema:
+    """An exponential moving average of the parameters, kept next to them and folded in after every applied update
+    (csrc/mlp/ema.h): ``e = fma(1 - d_t, p - e, e)`` with ``d_t = decay``, or with ``warmup``
+    ``min(decay, (1 + t) / (10 + t))``, t the 0-based count of averaged updates -- torch.lerp(e, p, 1 - d) and
+    torch.optim.swa_utils.get_ema_multi_avg_fn.  The average starts as a copy of the parameters."""
+    decay: float = 0.999
+    warmup: bool = False
+
+    def __post_init__(self):
+        if not 0.0 <= float(self.decay) < 1.0:
+            raise ValueError(f"decay must be in [0, 1), got {self.decay}")
+
+    def decay_at(self, t: int) -> float:
+        """d_t in fp64, as the header forms it."""
+        d = float(self.decay)
+        if not self.warmup:
+            return d
+        return min(d, (1.0 + float(t)) / (10.0 + float(t)))
+
+    def key(self) -> tuple:
+        return ("ema", float(self.decay), bool(self.warmup))
+
+    def as_meta(self) -> dict:
+        return {"decay": float(self.decay), "warmup": bool(self.warmup)}
+
+    @classmethod
+    def from_meta(cls, d: dict | None) -> "Ema | None":
+        return cls(float(d["decay"]), bool(d.get("warmup", False))) if d else None
+
+
+def resolve_ema(ema) -> Ema | None:
+    if ema is not None and not isinstance(ema, Ema):
+        raise TypeError("ema must be an Ema or None")
+    return ema
+
+
+def new_ema_state(nn) -> dict:
+    """A fresh host state of the average for ``models.mlp.train(ema=, ema_state=)``: {"t": 0, "avg": a copy of the
+    parameters, fp64 over [W1|b1|W2|b2]}."""
+    W1, b1, W2, b2 = nn.params
+    return {"t": 0, "avg": np.concatenate([np.asarray(a, np.float64).reshape(-1) for a in (W1, b1, W2, b2)])}
+
+
 def resolve(opt) -> Optimizer | None:
     """None / Optimizer.sgd() -> None (the plain-SGD code as it stands); a stateful Optimizer -> itself."""
     if opt is None:

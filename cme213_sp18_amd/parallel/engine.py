@@ -21,6 +21,8 @@ Two interchangeable compute backends execute a step:
 """
 from __future__ import annotations
 
+import types
+
 import numpy as np
 import torch
 
@@ -183,6 +185,10 @@ class MlpEngine:
         # keeping the best validation weights (enable_keep_best): None = nothing allocated, nothing launched; else the
         # rule, the best arena, the per-workgroup records (csrc/mlp/best.h) and, for data parallel, the [R][3] rows
         self._best = None
+        # an exponential moving average of the parameters (set_ema): None = nothing allocated, nothing launched; else
+        # the rule, the averaged arena, the per-workgroup records (csrc/mlp/ema.h) and, once an evaluation has read the
+        # average, its own derived copies of W1 and (split paths) the MlpStep bound to them
+        self._ema = None
 
     def _configure_path(self):
         dev = self.device
@@ -436,6 +442,8 @@ class MlpEngine:
             for dst, src in ((self.W1, W1), (self.b1, b1), (self.W2, W2), (self.b2, b2)):
                 dst.copy_(torch.as_tensor(np.asarray(src)).to(dst.dtype))
             self.refresh_shadow()
+        if self._ema is not None:
+            self.reset_ema()
 
     def dz1(self) -> torch.Tensor:
         """The last step's dZ1 as [H][ld] row-major.  A whole hip step with fp32 dZ1 leaves it only in the
@@ -553,49 +561,57 @@ class MlpEngine:
 
     def _hip_step(self):
         if self._step is None:
-            m = hip()
-            s = m.MlpStep()
-            loaded = self.X is not None
-            ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
-            b = dict(dt=DTYPE_CODES[self.dtype], P=self.P, H=self.H, C=self.C, ld=self.ld,
-                     X=ptr(self.X), labels=ptr(self.labels), XT=ptr(self.XT), Xw=ptr(self.Xw), XTw=ptr(self.XTw),
-                     N=self.num_samples if loaded else 0,
-                     W1=ptr(self.W1), b1=ptr(self.b1), W2=ptr(self.W2), b2=ptr(self.b2), W1g=ptr(self.W1g),
-                     gW1=ptr(self.gW1), gb1=ptr(self.gb1), gW2=ptr(self.gW2), gb2=ptr(self.gb2),
-                     gstatus=self.grads[self.status_index:].data_ptr(),
-                     a1=ptr(self.a1), D=ptr(self.D), dZ1=ptr(self.dZ1), dZ1g=ptr(self.dZ1g), loss=ptr(self.loss_buf),
-                     act=1, z2p=ptr(self.z2buf))
-            if self.np:
-                b.update(split=1, xscale=float(self.xscale), npw=self.np, npz=self.np, W1p=ptr(self.W1p),
-                         dZ1p=ptr(self.dZ1p))
-            if self.fh_counters is not None:
-                b.update(fh_counters=ptr(self.fh_counters), fh_tiles=int(self.fh_counters.numel()),
-                         ag_counters=ptr(self.ag_counters), ag_slabs=ptr(self.ag_slabs),
-                         w1s=ptr(self.W1s), xs=ptr(self.Xs), dz1s=ptr(self.dZ1s))
-            elif self.ag_gran is not None:  # the wide fused head
-                b.update(fh_tiles=int(self.ag_counters.numel()) // 64,  # [2 tilings][tiles][32]
-                         ag_gran=ptr(self.ag_gran), ag_gran_count=int(self.ag_gran.numel()),
-                         ag_counters=ptr(self.ag_counters), dz1s=ptr(self.dZ1s))
-            if self.kpart is not None:
-                b.update(kpart=ptr(self.kpart), kpart_cap=int(self.kpart.numel()))
-            bias_col = bool(self.np and self.XT is not None and self.XT.shape[0] == self.P + 1)
-            b.update(bias_col=int(bias_col))
-            s.bind(b)
-            s.shift = int(self.shift)
-            s.dw2p = ptr(self.dw2buf)
-            if self.ag_err is not None and (self.fh_counters is not None or self.ag_gran is not None):
-                s.ag_err = self.ag_err.data_ptr()
-                s.fh_allgather = int(self.fh_allgather)
-            if self.np:
-                # a new step cannot know whether an earlier one left the planes stale: re-split once
-                s.planes_stale = True
-                s.lazy_planes = int(self.lazy_planes)
-            s.store_a1 = int(self.store_a1)
-            s.ag_test_skip, s.ag_wait_us = self._ag_test_skip, self._ag_wait_us
-            if self._xgmi_fuse is not None and bias_col:
-                s.set_xgmi(*self._xgmi_fuse)
-            self._step = s
+            self._step = self._new_step()
         return self._step
+
+    def _new_step(self, weights=None):
+        """An MlpStep bound to the engine's buffers.  ``weights`` = (W1, b1, W2, b2, W1g, W1p): another set of
+        weights with its own derived copies of W1 (the averaged evaluation: it never runs a training step, so it
+        gets no fragment-ordered copy and no xGMI attachment); None: the engine's own."""
+        own = weights is None
+        W1, b1, W2, b2, W1g, W1p = (self.W1, self.b1, self.W2, self.b2, self.W1g, self.W1p) if own else weights
+        m = hip()
+        s = m.MlpStep()
+        loaded = self.X is not None
+        ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
+        b = dict(dt=DTYPE_CODES[self.dtype], P=self.P, H=self.H, C=self.C, ld=self.ld,
+                 X=ptr(self.X), labels=ptr(self.labels), XT=ptr(self.XT), Xw=ptr(self.Xw), XTw=ptr(self.XTw),
+                 N=self.num_samples if loaded else 0,
+                 W1=ptr(W1), b1=ptr(b1), W2=ptr(W2), b2=ptr(b2), W1g=ptr(W1g),
+                 gW1=ptr(self.gW1), gb1=ptr(self.gb1), gW2=ptr(self.gW2), gb2=ptr(self.gb2),
+                 gstatus=self.grads[self.status_index:].data_ptr(),
+                 a1=ptr(self.a1), D=ptr(self.D), dZ1=ptr(self.dZ1), dZ1g=ptr(self.dZ1g), loss=ptr(self.loss_buf),
+                 act=1, z2p=ptr(self.z2buf))
+        if self.np:
+            b.update(split=1, xscale=float(self.xscale), npw=self.np, npz=self.np, W1p=ptr(W1p),
+                     dZ1p=ptr(self.dZ1p))
+        if self.fh_counters is not None:
+            b.update(fh_counters=ptr(self.fh_counters), fh_tiles=int(self.fh_counters.numel()),
+                     ag_counters=ptr(self.ag_counters), ag_slabs=ptr(self.ag_slabs),
+                     w1s=ptr(self.W1s) if own else 0, xs=ptr(self.Xs), dz1s=ptr(self.dZ1s))
+        elif self.ag_gran is not None:  # the wide fused head
+            b.update(fh_tiles=int(self.ag_counters.numel()) // 64,  # [2 tilings][tiles][32]
+                     ag_gran=ptr(self.ag_gran), ag_gran_count=int(self.ag_gran.numel()),
+                     ag_counters=ptr(self.ag_counters), dz1s=ptr(self.dZ1s))
+        if self.kpart is not None:
+            b.update(kpart=ptr(self.kpart), kpart_cap=int(self.kpart.numel()))
+        bias_col = bool(self.np and self.XT is not None and self.XT.shape[0] == self.P + 1)
+        b.update(bias_col=int(bias_col))
+        s.bind(b)
+        s.shift = int(self.shift)
+        s.dw2p = ptr(self.dw2buf)
+        if self.ag_err is not None and (self.fh_counters is not None or self.ag_gran is not None):
+            s.ag_err = self.ag_err.data_ptr()
+            s.fh_allgather = int(self.fh_allgather)
+        if self.np:
+            # a new step cannot know whether an earlier one left the planes stale: re-split once
+            s.planes_stale = True
+            s.lazy_planes = int(self.lazy_planes)
+        s.store_a1 = int(self.store_a1)
+        s.ag_test_skip, s.ag_wait_us = self._ag_test_skip, self._ag_wait_us
+        if own and self._xgmi_fuse is not None and bias_col:
+            s.set_xgmi(*self._xgmi_fuse)
+        return s
 
     # ------------------------------------------------ xGMI all-reduce fused into the wgrad launch
     def fused_allreduce_slots(self) -> int:
@@ -981,9 +997,15 @@ class MlpEngine:
         return float(self.loss_buf.double().sum().item())
 
     # --------------------------------------------------------------- predict
-    def predict(self, x, chunk: int | None = None) -> np.ndarray:
-        """argmax labels for samples ``x`` ([N][P], host or device); GPU forward."""
+    def predict(self, x, chunk: int | None = None, weights: str = "current") -> np.ndarray:
+        """argmax labels for samples ``x`` ([N][P], host or device); GPU forward.  ``weights="ema"``: with the
+        averaged weights (set_ema), their derived copies of W1 rebuilt first; the live parameters are not touched."""
         self.join()
+        w = self._weights_for(weights)
+        W1g, b1, W2, b2 = (self.W1g, self.b1, self.W2, self.b2) if w is None else (w["W1g"], w["b1"], w["W2"], w["b2"])
+        step = None
+        if self.backend == "hip" and self.np:
+            step = self._hip_step() if w is None else self._ema_step()
         xt = torch.as_tensor(np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x)
         n = int(xt.shape[0])
         out = torch.empty(n, dtype=torch.int32, device=self.device)
@@ -991,6 +1013,8 @@ class MlpEngine:
         a1 = torch.empty(self.H, _round_up(chunk, 16), dtype=self.pdt, device=self.device)
         if self.backend == "hip":
             self._hip_step()
+        if w is not None:
+            self._ema_derive()
         for s in range(0, n, chunk):
             e = min(n, s + chunk)
             if self.np:  # raw uint8 pixels, scaled inside the kernel
@@ -1004,21 +1028,22 @@ class MlpEngine:
                     xb = xb / 255.0
                 xb = xb.to(self.gdt).contiguous()
             if self.backend == "hip" and self.np:
-                self._hip_step().predict(xb.data_ptr(), e - s, a1.data_ptr(), a1.shape[1], out[s:e].data_ptr(),
-                                         torch.cuda.current_stream(self.device).cuda_stream)
+                step.predict(xb.data_ptr(), e - s, a1.data_ptr(), a1.shape[1], out[s:e].data_ptr(),
+                             torch.cuda.current_stream(self.device).cuda_stream)
             elif self.backend == "hip":
                 m = hip()
                 st = torch.cuda.current_stream(self.device).cuda_stream
                 dt = DTYPE_CODES[self.dtype]
-                m.mlp_forward1(dt, self.W1g.data_ptr(), self.b1.data_ptr(), xb.data_ptr(), self.P, self.H, e - s,
+                m.mlp_forward1(dt, W1g.data_ptr(), b1.data_ptr(), xb.data_ptr(), self.P, self.H, e - s,
                                a1.data_ptr(), a1.shape[1], 1, st)
-                m.mlp_head(dt if self.dtype != "bf16" else 0, 1, a1.data_ptr(), a1.shape[1], self.W2.data_ptr(),
-                           self.b2.data_ptr(), H=self.H, C=self.C, n=e - s, pred=out[s:e].data_ptr(), stream=st)
+                m.mlp_head(dt if self.dtype != "bf16" else 0, 1, a1.data_ptr(), a1.shape[1], W2.data_ptr(),
+                           b2.data_ptr(), H=self.H, C=self.C, n=e - s, pred=out[s:e].data_ptr(), stream=st)
             else:
                 with torch.no_grad():
-                    W1e = self.W1p.to(self.pdt).sum(0) if self.np else self.W1g.to(self.pdt)
-                    z1 = (xb.to(self.pdt) * self.xscale) @ W1e.t() + self.b1
-                    z2 = torch.sigmoid(z1) @ self.W2.t() + self.b2
+                    W1p = self.W1p if w is None else w["W1p"]
+                    W1e = W1p.to(self.pdt).sum(0) if self.np else W1g.to(self.pdt)
+                    z1 = (xb.to(self.pdt) * self.xscale) @ W1e.t() + b1
+                    z2 = torch.sigmoid(z1) @ W2.t() + b2
                     out[s:e] = z2.argmax(dim=1).to(torch.int32)
         return out.cpu().numpy()
 
@@ -1089,14 +1114,19 @@ class MlpEngine:
             raise IndexError(f"evaluation slot {slot} outside [0, {ev['stats'].shape[0]})")
         return ev
 
-    def enqueue_eval(self, slot: int, first: int = 0, count: int | None = None) -> None:
+    def enqueue_eval(self, slot: int, first: int = 0, count: int | None = None, weights: str = "current") -> None:
         """Enqueue the evaluation of validation samples [first, first + count) into stats slot ``slot`` on the
         current stream, chunk by chunk: forward GEMM into the a1 scratch, then the evaluation head.  The first chunk
-        clears the slot.  No host read, no sync, no allocation: legal under stream capture."""
+        clears the slot.  No host read, no sync, no allocation: legal under stream capture.  ``weights="ema"``
+        evaluates the averaged weights (set_ema) through their own derived copies of W1, rebuilt on the stream ahead of
+        the first chunk; the live parameters are never overwritten."""
         ev = self._eval_set(slot)
         count = ev["n"] - first if count is None else int(count)
         if first < 0 or count < 0 or first + count > ev["n"]:
             raise IndexError("evaluation range outside the resident validation set")
+        if self._weights_for(weights) is not None:
+            self._enqueue_eval_ema(ev, int(slot), int(first), count)
+            return
         if self.backend != "hip":
             self._torch_eval(ev, int(slot), int(first), count)
             return
@@ -1123,9 +1153,11 @@ class MlpEngine:
                 m.mlp_eval_head(0 if self.dtype == "bf16" else dt, a1, lda, self.W2.data_ptr(), self.b2.data_ptr(),
                                 l0 + 4 * s, self.H, self.C, nb, stats, part, zero, st)
 
-    def _torch_eval(self, ev, slot: int, first: int, count: int) -> None:
-        """The evaluation head's math in torch ops (param dtype z2 and nll, fp64 loss accumulation)."""
+    def _torch_eval(self, ev, slot: int, first: int, count: int, w: dict | None = None) -> None:
+        """The evaluation head's math in torch ops (param dtype z2 and nll, fp64 loss accumulation).  ``w``: another
+        set of weights (the averaged ones) with their derived copies of W1; None: the engine's own."""
         C = self.C
+        src = self if w is None else types.SimpleNamespace(**w)
         with torch.no_grad():
             row = ev["stats"][slot]
             row.zero_()
@@ -1134,9 +1166,9 @@ class MlpEngine:
             step = ev["chunk"]
             for s in range(first, first + count, step):
                 e = min(first + count, s + step)
-                W1e = self.W1p.to(self.pdt).sum(0) if self.np else self.W1g.to(self.pdt)
-                z1 = (ev["X"][s:e].to(self.pdt) * self.xscale) @ W1e.t() + self.b1
-                z2 = torch.sigmoid(z1) @ self.W2.t() + self.b2
+                W1e = src.W1p.to(self.pdt).sum(0) if self.np else src.W1g.to(self.pdt)
+                z1 = (ev["X"][s:e].to(self.pdt) * self.xscale) @ W1e.t() + src.b1
+                z2 = torch.sigmoid(z1) @ src.W2.t() + src.b2
                 lab = ev["labels"][s:e].long()
                 mx = z2.max(dim=1, keepdim=True).values
                 pred = torch.where(z2 == mx, cls, C).min(dim=1).values  # the first maximum
@@ -1164,8 +1196,8 @@ class MlpEngine:
         ev = self._eval_set(slot)
         return self.unpack_eval(ev["stats"][int(slot)].cpu())
 
-    def evaluate(self, slot: int = 0, first: int = 0, count: int | None = None) -> dict:
-        self.enqueue_eval(slot, first, count)
+    def evaluate(self, slot: int = 0, first: int = 0, count: int | None = None, weights: str = "current") -> dict:
+        self.enqueue_eval(slot, first, count, weights=weights)
         return self.read_eval(slot)
 
     # ------------------------------------------------------- keep the best weights
@@ -1257,7 +1289,7 @@ class MlpEngine:
             rows.zero_()
             rows[int(rank)].copy_(torch.from_numpy(self._slot_triple(ev, slot)[0]))
 
-    def enqueue_keep_best(self, slot: int, rows=None) -> None:
+    def enqueue_keep_best(self, slot: int, rows=None, weights: str = "current") -> None:
         """One decision on the current stream, behind enqueue_eval(slot): from stats slot ``slot`` (one process) or from
         ``rows`` (a [R][3] float64 tensor of {n, correct, loss_sum} per rank, summed in rank order; on the hip backend
         a device tensor that stays alive until the launch has run -- best_rows is the resident one).  When the metric
@@ -1268,6 +1300,9 @@ class MlpEngine:
         monitor, min_delta, patience = b["rule"]
         code = self.BEST_MONITORS[monitor]
         b["fresh"] = False
+        # (weights="ema": the evaluation behind this decision read the averaged weights, so those are the ones kept)
+        w = self._weights_for(weights)
+        params = self.params if w is None else w["arena"]
         if rows is not None and (rows.dtype != torch.float64 or rows.ndim != 2 or rows.shape[1] != 3
                                  or rows.shape[0] < 1 or not rows.is_contiguous()):
             raise ValueError("rows must be a contiguous [R][3] float64 tensor, R >= 1")
@@ -1275,7 +1310,7 @@ class MlpEngine:
             if rows is not None and rows.device != self.device:
                 raise ValueError("rows must live on the engine's device")
             hip().mlp_keep_best(0 if self.pdt == torch.float32 else 1, code, min_delta, patience,
-                                self.params.data_ptr(), b["arena"].data_ptr(), self.best_count, b["rec"].data_ptr(),
+                                params.data_ptr(), b["arena"].data_ptr(), self.best_count, b["rec"].data_ptr(),
                                 int(b["rec"].shape[0]),
                                 0 if rows is not None else
                                 ev["stats"].data_ptr() + int(slot) * ev["stats"].shape[1] * 8,
@@ -1288,7 +1323,7 @@ class MlpEngine:
             rec, improved = cpu().best_decide(b["rec"][0].cpu().numpy(), code, min_delta, patience, triples)
             b["rec"].copy_(torch.from_numpy(rec).expand_as(b["rec"]))
             if improved:
-                b["arena"].copy_(self.params[:self.best_count])
+                b["arena"].copy_(params[:self.best_count])
 
     def best_state(self) -> dict:
         """Record 0 as a dict: evals, best_index, best_metric, bad, stopped, stop_index, last_metric (+ the rule:
@@ -1344,3 +1379,201 @@ class MlpEngine:
                     dst.copy_(src.reshape(dst.shape).to(dst.dtype))
             b["rec"].copy_(torch.from_numpy(rec).expand_as(b["rec"]))
         b["fresh"] = False
+
+    # ------------------------------------------------------- an average of the weights
+    @property
+    def ema_count_elems(self) -> int:
+        """Elements the averaging launch covers: the arena [W1|b1|W2|b2] without the status element."""
+        return int(self.layout.status)
+
+    def set_ema(self, rule) -> None:
+        """Keep an exponential moving average of the parameters on the device (optim.Ema, csrc/mlp/ema.h): allocates the
+        averaged arena (the parameter dtype, the layout of the parameter arena; bf16 mode's masters are fp32) and the
+        records {t, d of the last update, 0, 0} (one per workgroup of the kernel's fixed grid on the hip backend, one
+        otherwise), and starts the average as a copy of the parameters with t = 0.  ``None`` releases everything: then
+        nothing is allocated and nothing is launched."""
+        from ..optim import resolve_ema
+
+        rule = resolve_ema(rule)
+        if rule is None:
+            self._ema = None
+            return
+        dev = self.device
+        nrec = int(hip().ema_grid(self.ema_count_elems)) if self.backend == "hip" else 1
+        arena = torch.zeros(self.layout.total, dtype=self.pdt, device=dev)
+        W1, b1, W2, b2 = self.layout.views(arena)
+        # (W1g / W1p / step: the average's own derived copies of W1, made by the first evaluation that reads it)
+        self._ema = dict(rule=rule, arena=arena, rec=torch.zeros(nrec, 4, dtype=torch.float64, device=dev),
+                         W1=W1, b1=b1, W2=W2, b2=b2, W1g=None, W1p=None, step=None, step_for=None)
+        self.reset_ema()
+
+    def _ema_set(self) -> dict:
+        if self._ema is None:
+            raise RuntimeError("set_ema() first")
+        return self._ema
+
+    def reset_ema(self) -> None:
+        """The average becomes a copy of the current parameters and the count 0 (set_ema and set_params do this)."""
+        a = self._ema_set()
+        with torch.no_grad():
+            n = self.ema_count_elems
+            a["arena"][:n].copy_(self.params[:n])
+            a["rec"].zero_()
+
+    def ema_update(self, status: bool = False) -> None:
+        """Fold the parameters into the average: ONE launch (csrc/mlp/ema.hip) behind an applied update, on the current
+        stream, no host sync, legal under stream capture.  ``status``: the update came from the gradient bucket
+        (gradient mode + apply), whose status element, when non-zero, says that it was not applied -- the launch then
+        changes nothing; the sticky hand-off word of the all-gather forward + head is passed wherever the engine has
+        one, for the same reason.  Without set_ema() this is a no-op."""
+        a = self._ema
+        if a is None:
+            return
+        r = a["rule"]
+        n = self.ema_count_elems
+        if self.backend == "hip":
+            hip().mlp_ema_step(0 if self.pdt == torch.float32 else 1, float(r.decay), int(bool(r.warmup)),
+                               self.params.data_ptr(), a["arena"].data_ptr(), n, a["rec"].data_ptr(),
+                               int(a["rec"].shape[0]),
+                               self.grads[self.status_index:].data_ptr() if status else 0,
+                               self.ag_err.data_ptr() if self.ag_err is not None else 0,
+                               torch.cuda.current_stream(self.device).cuda_stream)
+            return
+        with torch.no_grad():
+            if status and float(self.grads[self.status_index]) != 0.0:
+                return
+            host = self.device.type == "cpu"
+            e, p = a["arena"][:n], self.params[:n]
+            ea, pa = (e, p) if host else (e.cpu(), p.cpu())
+            t = int(a["rec"][0, 0].item())
+            t1 = cpu().ema_step(ea.numpy(), pa.numpy(), float(r.decay), bool(r.warmup), t)
+            if not host:
+                e.copy_(ea)
+            d = float(cpu().ema_decay(float(r.decay), bool(r.warmup), t))
+            a["rec"].copy_(torch.tensor([float(t1), d, 0.0, 0.0], dtype=torch.float64).expand_as(a["rec"]))
+
+    def ema_count(self) -> int:
+        """The count of averaged updates (the device-resident record).  Synchronises."""
+        return int(self._ema_set()["rec"][0, 0].item())
+
+    def ema_records(self) -> np.ndarray:
+        """Every workgroup's record as raw doubles [nrec][4] (tests and diagnostics).  Synchronises."""
+        return self._ema_set()["rec"].cpu().numpy().copy()
+
+    def ema_state(self) -> dict:
+        """{decay, warmup, t, last_decay}: the rule and record 0.  Checks that every workgroup's record agrees.
+        Synchronises."""
+        a = self._ema_set()
+        rec = a["rec"].cpu()
+        if not bool((rec == rec[0]).all()):
+            raise RuntimeError("averaging records disagree: " + str(rec[:, :2].unique(dim=0).tolist()))
+        return {"decay": float(a["rule"].decay), "warmup": bool(a["rule"].warmup), "t": int(rec[0, 0]),
+                "last_decay": float(rec[0, 1])}
+
+    def ema_params(self):
+        """Host float64 copies (W1, b1, W2, b2) of the averaged weights, unpadded, as get_params()."""
+        a = self._ema_set()
+        return tuple(a[k].detach().to("cpu", torch.float64).numpy().copy() for k in ("W1", "b1", "W2", "b2"))
+
+    def set_ema_state(self, t: int, params=None, last_decay: float = 0.0) -> None:
+        """Resume: the count of averaged updates and (W1, b1, W2, b2) of the average (None: the arena is left as it
+        is)."""
+        a = self._ema_set()
+        if int(t) < 0:
+            raise ValueError("t must be >= 0")
+        with torch.no_grad():
+            if params is not None:
+                for k, src in zip(("W1", "b1", "W2", "b2"), params):
+                    src = torch.as_tensor(np.asarray(src))
+                    if src.numel() != a[k].numel():
+                        raise ValueError("averaged weights of another shape")
+                    a[k].copy_(src.reshape(a[k].shape).to(a[k].dtype))
+            rec = torch.tensor([float(int(t)), float(last_decay), 0.0, 0.0], dtype=torch.float64)
+            a["rec"].copy_(rec.expand_as(a["rec"]))
+
+    def adopt_ema(self) -> None:
+        """Make the average the current weights: a device copy into the parameter arena, then the bf16 planes / shadow
+        of W1 re-derived, as restore_best() does.  The average and its count stay as they are."""
+        a = self._ema_set()
+        with torch.no_grad():
+            n = self.ema_count_elems
+            self.params[:n].copy_(a["arena"][:n])
+            self.refresh_shadow()
+        self.mark_planes_stale()
+
+    def _weights_for(self, weights: str) -> dict | None:
+        """None for "current"; the averaging state for "ema" (with its derived copies of W1 allocated)."""
+        if weights == "current":
+            return None
+        if weights != "ema":
+            raise ValueError('weights must be "current" or "ema"')
+        a = self._ema_set()
+        if self.np and a["W1p"] is None:
+            a["W1p"] = torch.zeros(self.np, self.H, self.P, dtype=torch.bfloat16, device=self.device)
+        if a["W1g"] is None:
+            if self.np or self.dtype != "bf16":
+                a["W1g"] = a["W1"]
+            else:
+                a["W1g"] = torch.zeros(self.H, self.P, dtype=torch.bfloat16, device=self.device)
+        if self.backend == "hip" and self.np:
+            self._ema_step()
+        return a
+
+    def _ema_step(self):
+        """The second MlpStep: the engine's buffers with the averaged weights and their own bf16 planes.  Created on
+        first use, and again when the engine's own step was rebuilt (its buffers changed)."""
+        a = self._ema_set()
+        main = self._hip_step()
+        if a["step"] is None or a["step_for"] is not main:
+            a["step"] = self._new_step((a["W1"], a["b1"], a["W2"], a["b2"], a["W1g"], a["W1p"]))
+            a["step_for"] = main
+        return a["step"]
+
+    def _ema_derive(self) -> None:
+        """Ahead of the first chunk of an averaged evaluation: the derived copies of the averaged W1 are stale (the
+        averaging launch maintains none).  Split paths on the hip backend mark the second step's planes stale, so its
+        existing re-split runs -- inside a capture too, where the replay cannot decide; the bf16 path converts the
+        shadow on the stream; the torch backend re-derives them as refresh_shadow() does."""
+        a = self._ema_set()
+        with torch.no_grad():
+            if self.np and self.backend == "hip":
+                a["step"].planes_stale = True
+            elif self.np:
+                r = a["W1"].clone()
+                for p in range(self.np):
+                    a["W1p"][p] = r.to(torch.bfloat16)
+                    r -= a["W1p"][p].to(torch.float32)
+            elif self.dtype == "bf16":
+                a["W1g"].copy_(a["W1"])
+
+    def _enqueue_eval_ema(self, ev, slot: int, first: int, count: int) -> None:
+        """enqueue_eval() with the averaged weights: the same launches, the weight pointers those of the averaged
+        arena and its derived copies."""
+        a = self._weights_for("ema")
+        self._ema_derive()
+        if self.backend != "hip":
+            self._torch_eval(ev, slot, first, count, w=a)
+            return
+        m = hip()
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        a1, lda = ev["a1"].data_ptr(), int(ev["a1"].shape[1])
+        stats = ev["stats"].data_ptr() + slot * ev["stats"].shape[1] * 8
+        part = ev["partials"].data_ptr()
+        x0, l0, xrow = ev["X"].data_ptr(), ev["labels"].data_ptr(), self.P * ev["X"].element_size()
+        step = min(ev["chunk"], lda)
+        dt = DTYPE_CODES[self.dtype]
+        hdt = 0 if self.dtype == "bf16" else dt
+        if count == 0:  # an empty shard still clears its slot
+            m.mlp_eval_head(hdt, 0, lda, a["W2"].data_ptr(), a["b2"].data_ptr(), 0, self.H, self.C, 0, stats, part, 1,
+                            st)
+            return
+        for s in range(first, first + count, step):
+            nb = min(step, first + count - s)
+            zero = int(s == first)
+            if self.np:
+                a["step"].evaluate(x0 + s * xrow, l0 + 4 * s, nb, a1, lda, stats, part, st, zero)
+            else:
+                m.mlp_forward1(dt, a["W1g"].data_ptr(), a["b1"].data_ptr(), x0 + s * xrow, self.P, self.H, nb, a1, lda,
+                               1, st)
+                m.mlp_eval_head(hdt, a1, lda, a["W2"].data_ptr(), a["b2"].data_ptr(), l0 + 4 * s, self.H, self.C, nb,
+                                stats, part, zero, st)

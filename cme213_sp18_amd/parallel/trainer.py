@@ -242,8 +242,14 @@ class DataParallelTrainer:
                  normalize: bool = False, path: str = "auto", allreduce: str = "auto", overlap: bool = True,
                  overlap_chunks: int = 0, fuse_allreduce: bool = True, executor: str = "auto",
                  grad_wire: str = "auto", fused_form: str = "auto", shuffle_seed: int | None = None,
-                 optimizer=None, schedule=None, clip_norm=None, augment=None):
+                 optimizer=None, schedule=None, clip_norm=None, augment=None, ema=None):
         self.nn = nn
+        # an exponential moving average of the parameters (optim.Ema; None: nothing allocated, nothing launched): one
+        # more launch behind every applied update folds the parameters into a resident averaged arena, on every sync
+        # path; evaluations, keep-best and adopt_ema() can then use the averaged weights
+        from ..optim import resolve_ema
+
+        self.ema = resolve_ema(ema)
         # the update rule (optim.Optimizer): None / Optimizer.sgd() = the plain-SGD code as it stands.  A stateful
         # rule (momentum, Adam) runs every step in gradient mode followed by engine.apply() -- one extra launch --
         # on every sync path; the fused forms (the update inside the weight-gradient launch, the fused xGMI
@@ -311,6 +317,7 @@ class DataParallelTrainer:
         self.engine.set_params(*nn.params)
         self.engine.set_optimizer(self.optimizer)
         self.engine.set_update_policy(self.schedule, self.clip_norm)
+        self.engine.set_ema(self.ema)
         # training reads nothing of a1 after a step: the wide fused forward + head launch skips its 13 MB store
         # at H = 4096 (bench/wide_ag_ab.py: -1.4 us/step fp32, -2.1 us bf16)
         self.engine.set_store_a1(False)
@@ -492,6 +499,9 @@ class DataParallelTrainer:
         if e._best is not None:  # ... and the same best weights and decisions
             w = torch.cat([w, as_words(e._best["arena"].detach().reshape(-1)).to(torch.int64),
                            e._best["rec"][0].view(torch.int64)])
+        if e._ema is not None:  # ... and the same averaged weights and count
+            w = torch.cat([w, as_words(e._ema["arena"].detach().reshape(-1)).to(torch.int64),
+                           e._ema["rec"][0].view(torch.int64)])
         idx = torch.arange(1, w.numel() + 1, device=w.device, dtype=torch.int64)
         # two position-weighted sums, folded below 2^52 so they travel exactly as float64
         h = [int(w.sum().item()) % (1 << 52), int(((w % 65521) * (idx % 65519)).sum().item()) % (1 << 52)]
@@ -608,12 +618,13 @@ class DataParallelTrainer:
                         "accuracy": r["correct"] / n if n else float("nan"), "confusion": r["confusion"]})
         return out
 
-    def evaluate(self) -> dict:
-        """Evaluate the resident validation set with the current parameters: dict(n, loss, accuracy, confusion) --
-        loss is the mean nll without the regulariser, confusion [C][C] with rows = labels.  Collective."""
+    def evaluate(self, weights: str = "current") -> dict:
+        """Evaluate the resident validation set with the current parameters (``weights="ema"``: the averaged ones):
+        dict(n, loss, accuracy, confusion) -- loss is the mean nll without the regulariser, confusion [C][C] with rows
+        = labels.  Collective."""
         if self.engine.eval_slots == 0:
             raise RuntimeError("load_eval() first")
-        self.engine.enqueue_eval(0)
+        self.engine.enqueue_eval(0, weights=weights)
         return self._read_evals(1)[0]
 
     def _check_fused(self) -> bool:
@@ -683,29 +694,46 @@ class DataParallelTrainer:
         off, n = self.shard(start, length)
         if self.schedule is not None:
             self._window_for_step()
+        # (with ``ema`` every branch ends with engine.ema_update(), a no-op without it: the averaging launch behind the
+        # applied update; the branches that apply the gradient bucket pass its status element along)
         if self.profiler is not None and n > 0:
             self._profiled_step(off, n, 1.0 / (n * self.R), reg, lr, with_loss)
             return
         if n == 0:  # fewer columns than ranks: only the regulariser contributes
             e.reg_only_grads(reg / self.R)
             self._allreduce_sgd(lr)
+            e.ema_update(status=True)
             return
         scale = 1.0 / (n * self.R)
         if self._apply_launch and isinstance(self.comm, NullComm) and self.allreduce_mode != "host":
             e.run(off, n, scale, reg, lr, sgd=False, with_loss=with_loss)  # 1 process: gradient mode + apply
             e.apply(lr)
+            e.ema_update(status=True)
         elif isinstance(self.comm, NullComm) and self.allreduce_mode != "host":  # 1 process: SGD fused into wgrad
             e.run(off, n, scale, reg, lr, sgd=True, with_loss=with_loss, pf_next=next_start)
+            e.ema_update()
         elif self.fused_allreduce:
             e.run(off, n, scale, reg / self.R, lr, sgd=2, with_loss=with_loss, pf_next=next_start)
+            e.ema_update()
         elif self._bucketed:
             self._step_bucketed(off, n, scale, reg / self.R, lr, with_loss)
+            e.ema_update(status=True)
         else:
             e.run(off, n, scale, reg / self.R, lr, sgd=False, with_loss=with_loss)
             self._allreduce_sgd(lr)
+            e.ema_update(status=True)
 
     def _profiled_step(self, off, n, scale, reg, lr, with_loss):
-        """The same step, split into timed phases (PhaseTimer events + roctx ranges; eager only)."""
+        """The same step, split into timed phases (PhaseTimer events + roctx ranges; eager only); with ``ema`` an
+        ``ema`` phase -- the averaging launch -- follows the update's."""
+        self._profiled_update(off, n, scale, reg, lr, with_loss)
+        if self.ema is not None:
+            fused = self.fused_allreduce or (
+                isinstance(self.comm, NullComm) and self.allreduce_mode != "host" and not self._apply_launch)
+            with self.profiler.phase("ema"):
+                self.engine.ema_update(status=not fused)
+
+    def _profiled_update(self, off, n, scale, reg, lr, with_loss):
         e, P = self.engine, self.profiler
         single = isinstance(self.comm, NullComm) and self.allreduce_mode != "host" and not self._apply_launch
         if e.backend != "hip":
@@ -805,10 +833,19 @@ class DataParallelTrainer:
         if e._best is not None:  # the best arena, every workgroup's record and the host's list of decisions
             snap += ({"arena": e._best["arena"].clone(), "rec": e._best["rec"].clone(),
                       "iters": len(self._best_iters)},)
+        if e._ema is not None:  # the averaged arena and every workgroup's record, tagged by name
+            snap += ({"kind": "ema", "arena": e._ema["arena"].clone(), "rec": e._ema["rec"].clone()},)
         return snap
 
     def _restore(self, snap):
         e = self.engine
+        # the optional entries behind the fixed ones are dicts; one with a "kind" names itself, the untagged one is
+        # keep-best's
+        tagged = {d["kind"]: d for d in snap if isinstance(d, dict) and "kind" in d}
+        snap = tuple(d for d in snap if not (isinstance(d, dict) and "kind" in d))
+        if "ema" in tagged and e._ema is not None:
+            e._ema["arena"].copy_(tagged["ema"]["arena"])
+            e._ema["rec"].copy_(tagged["ema"]["rec"])
         e.params.copy_(snap[0])
         if snap[1] is not None:
             e.W1g.copy_(snap[1])
@@ -829,7 +866,8 @@ class DataParallelTrainer:
         key = (tuple(plan.steps), float(lr), float(reg)) + (
             (self.optimizer.key(),) if self.optimizer is not None else ()) + (
             (("schedule",) + self.schedule.key(),) if self.schedule is not None else ()) + (
-            (("clip", float(self.clip_norm)),) if self.clip_norm is not None else ())
+            (("clip", float(self.clip_norm)),) if self.clip_norm is not None else ()) + (
+            (self.ema.key(),) if self.ema is not None else ())
         g = self._graphs.get(key)
         if g is not None:
             return g
@@ -854,6 +892,13 @@ class DataParallelTrainer:
         a fused step (one process, or the xGMI all-reduce fused into wgrad) and consecutive full global
         batches (wrapping to 0 at the end of the dataset); else None."""
         e = self.engine
+        if self.ema is not None:
+            self.native_reason = ("weight averaging (ema): the averaging launch follows every update, so a plan cannot "
+                                  "run as one launch; every step is replayed from the epoch graph with that launch "
+                                  "behind it")
+            if e.backend == "hip":
+                e._hip_step().xstep_reason = self.native_reason
+            return None
         if self.optimizer is not None:
             self.native_reason = (f"stateful optimizer ({self.optimizer.kind}): every step runs in gradient mode "
                                   "followed by the optimizer launch")
@@ -996,7 +1041,8 @@ class DataParallelTrainer:
     def train(self, epochs: int, lr: float, reg: float, print_every: int = 0, debug: bool = False,
               outdir: str = "Outputs", log=print, on_event=None, fault: tuple[int, int] | None = None,
               diff_file=None, eval_every: int = 0, shuffle_seed: int | None = None, keep_best: str | None = None,
-              patience: int | None = None, min_delta: float = 0.0, stop_check_every: int = 0) -> TrainStats:
+              patience: int | None = None, min_delta: float = 0.0, stop_check_every: int = 0,
+              eval_weights: str | None = None) -> TrainStats:
         """Full training loop (neural_network.cpp:446-555).  Eager steps where the
         host must look at a step (loss printing / debug diffs), graphs elsewhere.
 
@@ -1054,6 +1100,18 @@ class DataParallelTrainer:
         parameters and the optimizer state after an early return are those of the epoch the host left at, not those of
         the best or of the stopping evaluation.  ``TrainStats.best`` / ``stopped`` / ``stop_index`` report the record.
 
+        With ``ema`` (the constructor's optim.Ema) one more launch behind every applied update folds the parameters into
+        the resident average (csrc/mlp/ema.h); the parameters themselves are bitwise those of a run without it.  The
+        average and its count live on the device across calls: train(2) + train(2) equals train(4) in both.
+        ``eval_weights`` = "ema" | "current" picks the weights the evaluations of this call read (None: "ema" when
+        averaging is on, else "current"); every evaluation record and event carries ``weights``.  An averaged
+        evaluation runs through the average's own derived copies of W1 and never overwrites the live parameters; with
+        keep_best the best arena then receives the averaged weights that were evaluated.  train() never adopts the
+        average by itself: adopt_ema() does.  The averaging launch skips an update that was not applied (the gradient
+        bucket's status element, the sticky hand-off word).  A peer-wait failure of the fused xGMI form is covered as
+        it is for the parameters: the epoch-start snapshot, which carries the average and its records, is restored, or
+        every rank raises.
+
         With the xGMI all-reduce, every epoch ends with a collective check of the peer-wait error flag
         (assert_comm_ok): a timed-out wait raises CommFailure on every rank before another epoch runs."""
         from ..utils.checkpoint import write_diff_gpu_cpu
@@ -1062,6 +1120,12 @@ class DataParallelTrainer:
             raise ValueError("patience, min_delta and stop_check_every need keep_best='loss' or 'accuracy'")
         if keep_best is not None and not int(eval_every) > 0:
             raise ValueError("train(keep_best=...) needs eval_every > 0: the rule acts on the evaluations")
+        if eval_weights is None:
+            eval_weights = "ema" if self.ema is not None else "current"
+        if eval_weights not in ("ema", "current"):
+            raise ValueError('eval_weights must be "ema", "current" or None')
+        if eval_weights == "ema" and self.ema is None:
+            raise ValueError('eval_weights="ema" needs a trainer with ema=Ema(...)')
         stop_check_every = max(0, int(stop_check_every))
         stats = TrainStats()
         plan = self.epoch_plan()
@@ -1080,6 +1144,7 @@ class DataParallelTrainer:
             if self.engine.eval_slots == 0:
                 raise RuntimeError("train(eval_every=...): load_eval() first")
             self.engine.reserve_eval_slots(max(1, n_ev))
+            self.engine._weights_for(eval_weights)  # (the average's derived copies are allocated up front)
         if keep_best is not None:
             self.engine.enable_keep_best(keep_best, min_delta, patience, ranks=self.R)
         best_epochs: dict = {}  # decision index -> epoch of this call
@@ -1103,7 +1168,8 @@ class DataParallelTrainer:
                     f"accuracy = {r['accuracy']:.6g} (n = {r['n']})")
             if on_event is not None:
                 on_event({"event": "eval", "epoch": epoch, "iter": self.iter, "n": r["n"], "loss": r["loss"],
-                          "accuracy": r["accuracy"]})
+                          "accuracy": r["accuracy"],
+                          **({"weights": eval_weights} if self.ema is not None else {})})
 
         def best_enqueued(epoch: int) -> None:
             """The decision behind this epoch's evaluation is on the stream: remember when it was taken and, where the
@@ -1141,9 +1207,9 @@ class DataParallelTrainer:
                     self.run_plan(plan, lr, reg)
                 slot = eval_slot(epoch)
                 if slot >= 0:  # behind the epoch's plan, ahead of the epoch's sync (if any)
-                    self.engine.enqueue_eval(slot)
+                    self.engine.enqueue_eval(slot, weights=eval_weights)
                     if keep_best is not None:
-                        self._enqueue_keep_best(slot)
+                        self._enqueue_keep_best(slot, eval_weights)
                 if xgmi_live or ag_live:
                     self.assert_comm_ok()  # syncs; every rank raises together
                 self.iter += len(plan.steps)
@@ -1190,9 +1256,9 @@ class DataParallelTrainer:
                 stats.images += (ln // self.R) * self.R
             slot = eval_slot(epoch)
             if slot >= 0:
-                self.engine.enqueue_eval(slot)
+                self.engine.enqueue_eval(slot, weights=eval_weights)
                 if keep_best is not None:
-                    self._enqueue_keep_best(slot)
+                    self._enqueue_keep_best(slot, eval_weights)
             if xgmi_live or ag_live:
                 self.assert_comm_ok()
             if slot >= 0:
@@ -1230,7 +1296,8 @@ class DataParallelTrainer:
                     recs = self._read_evals(n_ev)
                     for s_ in done:
                         ev_read.setdefault(s_, recs[s_])
-                stats.evals = [{"epoch": ev_meta[s_][0], "iter": ev_meta[s_][1], **ev_read[s_]} for s_ in done]
+                stats.evals = [{"epoch": ev_meta[s_][0], "iter": ev_meta[s_][1], **ev_read[s_],
+                                **({"weights": eval_weights} if self.ema is not None else {})} for s_ in done]
             if keep_best is not None:
                 st = self.engine.best_state()
                 stats.stopped, stats.stop_index = st["stopped"], st["stop_index"]
@@ -1251,13 +1318,13 @@ class DataParallelTrainer:
         return stats
 
     # ------------------------------------------------------- keep the best weights
-    def _enqueue_keep_best(self, slot: int) -> None:
+    def _enqueue_keep_best(self, slot: int, weights: str = "current") -> None:
         """The decision behind enqueue_eval(slot).  One rank: the launch reads the stats slot itself.  R > 1: pack this
         rank's triple into its row, SUM all-reduce the [R][3] rows (an exact all-gather: every other rank wrote zeros),
         decide from the rows -- on-stream for RCCL, through a host copy for host-side communicators, as _read_evals."""
         e = self.engine
         if self.R == 1:
-            e.enqueue_keep_best(slot)
+            e.enqueue_keep_best(slot, weights=weights)
             return
         from .comm import TorchDistComm
 
@@ -1275,7 +1342,7 @@ class DataParallelTrainer:
             rows.copy_(g)
         else:
             self.comm.allreduce_(rows)
-        e.enqueue_keep_best(slot, rows)
+        e.enqueue_keep_best(slot, rows, weights=weights)
 
     def enable_keep_best(self, monitor: str = "loss", min_delta: float = 0.0, patience: int | None = None) -> None:
         """What train(keep_best=...) does on entry; needed by hand only ahead of set_best_state() on a resume."""
@@ -1306,6 +1373,24 @@ class DataParallelTrainer:
         self.engine.set_best_state(record, params)
         self._best_iters = list(iters) if iters is not None else []
 
+    # ------------------------------------------------------- an average of the weights
+    def ema_params(self):
+        """Host float64 copies (W1, b1, W2, b2) of the averaged weights."""
+        return self.engine.ema_params()
+
+    def ema_state(self) -> dict:
+        return self.engine.ema_state()
+
+    def set_ema_state(self, t: int, params=None) -> None:
+        """Resume: the count and the averaged weights of a checkpoint."""
+        self.engine.set_ema_state(t, params)
+
+    def adopt_ema(self) -> None:
+        """Make the averaged weights the current ones (a device copy, then ``nn``): what train() never does by itself.
+        The iteration counter, the optimizer state and the average itself stay as they are."""
+        self.engine.adopt_ema()
+        self.sync_to(self.nn)
+
     def sync_to(self, nn) -> None:
         W1, b1, W2, b2 = self.engine.get_params()
         nn.W[0][...] = W1
@@ -1313,8 +1398,8 @@ class DataParallelTrainer:
         nn.W[1][...] = W2
         nn.b[1][...] = b2
 
-    def predict(self, x) -> np.ndarray:
-        return self.engine.predict(x)
+    def predict(self, x, weights: str = "current") -> np.ndarray:
+        return self.engine.predict(x, weights=weights)
 
 
 def parallel_train(nn, X, y, learning_rate: float, reg: float = 0.0, epochs: int = 15, batch_size: int = 800,

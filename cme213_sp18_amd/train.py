@@ -63,8 +63,8 @@ def run(cfg: TrainConfig) -> dict:
     from .optim import Optimizer
     from .parallel.launcher import PlacementError, init_distributed, shutdown, verify_placement
     from .parallel.trainer import DataParallelTrainer
-    from .utils.checkpoint import (checkNNErrors, load_best_state, load_checkpoint, load_optim_state,
-                                   save_checkpoint)
+    from .utils.checkpoint import (checkNNErrors, load_best_state, load_checkpoint, load_ema_state,
+                                   load_optim_state, save_checkpoint)
     from .utils.common import precision, save_label
     from .utils.data import load_dataset
 
@@ -84,7 +84,8 @@ def run(cfg: TrainConfig) -> dict:
         aug = cfg.augment  # an augment.Shift or None
         jlog({"event": "config", "world": world, "device": str(device), **placement, **{
             k: v for k, v in vars(cfg).items() if isinstance(v, (int, float, str, bool))},
-            "augment": aug.to_meta() if aug is not None else None})
+            "augment": aug.to_meta() if aug is not None else None,
+            "ema": cfg.ema_rule.as_meta() if cfg.ema_rule is not None else None})
         log0(rank, f"Number of processes = {world}")
         log0(rank, f"Device = {device} ({torch.cuda.get_device_name(device) if device.type == 'cuda' else 'cpu'})")
         if cfg.grade == 4:
@@ -110,6 +111,9 @@ def run(cfg: TrainConfig) -> dict:
         best_rule = ({"monitor": cfg.keep_best, "min_delta": float(cfg.min_delta), "patience": cfg.patience}
                      if cfg.keep_best else None)
         best_saved = None  # the checkpoint's keep-best state (continued when the flags agree)
+        ema = cfg.ema_rule  # an optim.Ema or None
+        ema_saved = None  # the checkpoint's averaged weights and count (continued when the flags agree)
+        seq_ema = None  # the sequential run's average (optim.new_ema_state)
         if cfg.resume:
             nn, meta = load_checkpoint(cfg.resume)
             log0(rank, f"Resumed from {cfg.resume}: {meta}")
@@ -136,6 +140,14 @@ def run(cfg: TrainConfig) -> dict:
                            f"{best_rule}: the best weights and the patience count do not continue the checkpoint's")
             elif saved_best is not None:
                 best_saved = saved_best
+            saved_ema = load_ema_state(cfg.resume, meta)
+            saved_ema_rule = {k: saved_ema[k] for k in ("decay", "warmup")} if saved_ema is not None else None
+            if saved_ema_rule != (ema.as_meta() if ema is not None else None):
+                log0(rank, f"warning: the checkpoint was trained with weight averaging {saved_ema_rule}, this run uses "
+                           f"{ema.as_meta() if ema is not None else None}: the average does not continue the "
+                           "checkpoint's" + (" (it starts from the resumed weights)" if ema is not None else ""))
+            elif saved_ema is not None:
+                ema_saved = saved_ema
             if meta.get("shuffle_seed") != cfg.shuffle_seed:
                 log0(rank, f"warning: the checkpoint was trained with --shuffle-seed {meta.get('shuffle_seed')}, this "
                            f"run uses {cfg.shuffle_seed}: the epochs' orders do not continue the checkpoint's")
@@ -154,12 +166,26 @@ def run(cfg: TrainConfig) -> dict:
         if rank == 0 and cfg.run_seq:
             log0(rank, "Start Sequential Training")
             t = time.perf_counter()
+            if ema is not None:
+                from .optim import new_ema_state
+
+                seq_ema = new_ema_state(seq_nn)
+                if ema_saved is not None:
+                    W1a, b1a, W2a, b2a = ema_saved["params"]
+                    seq_ema = {"t": ema_saved["t"], "avg": np.concatenate(
+                        [np.asarray(a, np.float64).reshape(-1) for a in (W1a, b1a, W2a, b2a)])}
             mlp.train(seq_nn, xs, ds.y_train, cfg.learning_rate, cfg.reg, cfg.num_epochs, cfg.batch_size,
                       False, cfg.print_every, cfg.debug, cfg.outdir, cfg.softmax_shift, cfg.ckpt_precision,
                       iter0=int(meta.get("iter", 0)), shuffle_seed=cfg.shuffle_seed, optimizer=opt,
-                      optim_state=copy.deepcopy(opt_state), schedule=sched, clip_norm=clip, augment=aug)
+                      optim_state=copy.deepcopy(opt_state), schedule=sched, clip_norm=clip, augment=aug, ema=ema,
+                      ema_state=seq_ema)
             out["seq_seconds"] = time.perf_counter() - t
             log0(rank, f"Time for Sequential Training: {out['seq_seconds']:.6f} seconds")
+            if cfg.use_ema:  # the sequential run's final weights are its average too
+                o = 0
+                for dst in seq_nn.params:
+                    dst[...] = seq_ema["avg"][o:o + dst.size].reshape(dst.shape)
+                    o += dst.size
             out["seq_dev_precision"] = precision(mlp.predict(seq_nn, xd, cfg.softmax_shift), ds.y_dev)
             log0(rank, f"Precision on validation set for sequential training = {out['seq_dev_precision']}")
         comm.barrier()  # the parallel run's debug diff reads the CPU snapshots
@@ -174,16 +200,18 @@ def run(cfg: TrainConfig) -> dict:
                                        backend=backend, shift=cfg.softmax_shift, normalize=cfg.normalize,
                                        path=cfg.path,
                                        allreduce=tp_allreduce_mode(cfg.allreduce), shuffle_seed=cfg.shuffle_seed,
-                                       optimizer=opt, schedule=sched, clip_norm=clip, augment=aug)
+                                       optimizer=opt, schedule=sched, clip_norm=clip, augment=aug, ema=ema)
             tr.use_graphs = cfg.use_graphs
         else:
             tr = DataParallelTrainer(nn, comm=comm, device=device, dtype=cfg.dtype, batch_size=cfg.batch_size,
                                      backend=backend, shift=cfg.softmax_shift, use_graphs=cfg.use_graphs,
                                      normalize=cfg.normalize, path=cfg.path, allreduce=cfg.allreduce,
                                      overlap_chunks=cfg.overlap_chunks, shuffle_seed=cfg.shuffle_seed, optimizer=opt,
-                                     schedule=sched, clip_norm=clip, augment=aug)
+                                     schedule=sched, clip_norm=clip, augment=aug, ema=ema)
             if opt_state is not None:
                 tr.engine.set_optim_state(opt_state)
+            if ema_saved is not None:
+                tr.set_ema_state(ema_saved["t"], ema_saved["params"])
         tr.load(ds.x_train, ds.y_train)
         eval_every = cfg.eval_every if cfg.parallel != "tp" else 0
         if cfg.eval_every > 0 and not eval_every:
@@ -191,6 +219,8 @@ def run(cfg: TrainConfig) -> dict:
         if eval_every > 0:
             tr.load_eval(ds.x_dev, ds.y_dev)
         train_kw = {"eval_every": eval_every} if eval_every > 0 else {}
+        if ema is not None and cfg.eval_weights:
+            train_kw["eval_weights"] = cfg.eval_weights
         if cfg.keep_best:
             train_kw.update(keep_best=cfg.keep_best, patience=cfg.patience, min_delta=cfg.min_delta,
                             stop_check_every=cfg.stop_check_every)
@@ -210,6 +240,11 @@ def run(cfg: TrainConfig) -> dict:
                                   **({"optimizer": opt.as_meta()} if opt.stateful else {}),
                                   **({"schedule": sched.as_meta()} if sched is not None else {}),
                                   **({"clip_norm": clip} if clip is not None else {})}
+
+        def ckpt_ema():
+            if ema is None:
+                return None
+            return {**ema.as_meta(), "t": tr.engine.ema_count(), "params": tr.ema_params()}
         ckpt_optim = lambda: tr.engine.optim_state() if keeps_state else None  # noqa: E731
 
         def ckpt_best():
@@ -238,7 +273,7 @@ def run(cfg: TrainConfig) -> dict:
             if cfg.ckpt_dir and done < cfg.num_epochs:
                 if rank == 0:
                     save_checkpoint(nn, cfg.ckpt_dir, meta=ckpt_meta(done), optim_state=ckpt_optim(),
-                                    best=ckpt_best())
+                                    best=ckpt_best(), ema=ckpt_ema())
                     jlog({"event": "checkpoint", "dir": cfg.ckpt_dir, "epochs": done})
                 comm.barrier()
             if k == 0:
@@ -263,6 +298,15 @@ def run(cfg: TrainConfig) -> dict:
                   "restored": bool(cfg.restore_best and bs["best_index"] >= 0),
                   **({k: st.best[k] for k in ("epoch", "loss", "accuracy")} if st.best else {})})
             out.update(best_index=bs["best_index"], best_metric=bs["best_metric"], stopped=bs["stopped"])
+        if ema is not None:
+            es = tr.ema_state()
+            if cfg.use_ema:
+                tr.adopt_ema()  # every rank: before the precision, the predictions and the final checkpoint
+            log0(rank, f"Weight averaging: decay {es['decay']:.10g}" + (" with warmup" if es["warmup"] else "")
+                 + f", {es['t']} update(s) averaged" + (" -- adopted" if cfg.use_ema else ""))
+            jlog({"event": "ema", "decay": es["decay"], "warmup": es["warmup"], "t": es["t"],
+                  "adopted": bool(cfg.use_ema)})
+            out.update(ema_t=es["t"])
         if tr.profiler is not None:
             phases = tr.profiler.summary()
             out["profile"] = phases
@@ -281,7 +325,8 @@ def run(cfg: TrainConfig) -> dict:
             if ds.y_test is not None:
                 out["par_test_precision"] = precision(pred, ds.y_test)
             if cfg.ckpt_dir:
-                save_checkpoint(nn, cfg.ckpt_dir, meta=ckpt_meta(done), optim_state=ckpt_optim(), best=ckpt_best())
+                save_checkpoint(nn, cfg.ckpt_dir, meta=ckpt_meta(done), optim_state=ckpt_optim(), best=ckpt_best(),
+                                ema=ckpt_ema())
             if (cfg.grade or cfg.debug) and cfg.run_seq:
                 log0(rank, "\nGrading mode on. Checking for correctness")
                 out["correct"] = checkNNErrors(seq_nn, nn, os.path.join(cfg.outdir, "NNErrors.txt"))

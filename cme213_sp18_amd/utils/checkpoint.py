@@ -128,7 +128,8 @@ def checkNNErrors(seq_nn, par_nn, path: str = "Outputs/NNErrors.txt", verbose: b
 
 
 def save_checkpoint(nn, directory: str, meta: dict | None = None, precision: int = 17,
-                    binary: bool = True, optim_state: dict | None = None, best: dict | None = None) -> None:
+                    binary: bool = True, optim_state: dict | None = None, best: dict | None = None,
+                    ema: dict | None = None) -> None:
     """Resume checkpoint: W0/W1/b0/b1 raw_ascii (exact fp64 by default) + JSON sidecar (+ .npz).
 
     ``optim_state`` (MlpEngine.optim_state(); None for plain SGD): the optimizer's state buffers go to ``optim.npz``
@@ -138,7 +139,11 @@ def save_checkpoint(nn, directory: str, meta: dict | None = None, precision: int
     ``best`` (train --keep-best; None otherwise): dict(monitor, min_delta, patience, record = the 8 doubles of the
     device's record, iter, iters = the iteration counter behind every decision, params = (W1, b1, W2, b2) of the best
     weights or None before any).  The weights go to ``best/{W0,W1,b0,b1}.mat`` as raw_ascii (exact fp64) and the rest
-    to the sidecar's ``best`` (a NaN metric is written as null)."""
+    to the sidecar's ``best`` (a NaN metric is written as null).
+
+    ``ema`` (train --ema; None otherwise): dict(decay, warmup, t = the count of averaged updates, params = (W1, b1, W2,
+    b2) of the averaged weights).  The weights go to ``ema/{W0,W1,b0,b1}.mat`` as raw_ascii (exact fp64) and {decay,
+    warmup, t} to the sidecar's ``ema``."""
     os.makedirs(directory, exist_ok=True)
     for name, m in zip(_NAMES, _mats(nn)):
         save_raw_ascii(os.path.join(directory, f"{name}.mat"), m, precision)
@@ -163,6 +168,13 @@ def save_checkpoint(nn, directory: str, meta: dict | None = None, precision: int
             W1, b1, W2, b2 = best["params"]
             for name, a in zip(_NAMES, (W1, W2, np.reshape(b1, (-1, 1)), np.reshape(b2, (-1, 1)))):
                 save_raw_ascii(os.path.join(bd, f"{name}.mat"), a, 17)
+    if ema is not None:
+        m["ema"] = {"decay": float(ema["decay"]), "warmup": bool(ema["warmup"]), "t": int(ema["t"])}
+        ed = os.path.join(directory, "ema")
+        os.makedirs(ed, exist_ok=True)
+        W1, b1, W2, b2 = ema["params"]
+        for name, a in zip(_NAMES, (W1, W2, np.reshape(b1, (-1, 1)), np.reshape(b2, (-1, 1)))):
+            save_raw_ascii(os.path.join(ed, f"{name}.mat"), a, 17)
     m["H"] = list(nn.H)
     with open(os.path.join(directory, "meta.json"), "w") as f:
         json.dump(m, f, indent=1, sort_keys=True)
@@ -181,6 +193,17 @@ def load_best_state(directory: str, meta: dict) -> dict | None:
         W0, W1, b0, b1 = (load_raw_ascii(os.path.join(bd, f"{n}.mat")) for n in _NAMES)
         out["params"] = (W0, b0.ravel(), W1, b1.ravel())
     return out
+
+
+def load_ema_state(directory: str, meta: dict) -> dict | None:
+    """The weight-averaging state a checkpoint holds (the ``ema`` dict of save_checkpoint), or None."""
+    e = meta.get("ema")
+    if not e:
+        return None
+    ed = os.path.join(directory, "ema")
+    W0, W1, b0, b1 = (load_raw_ascii(os.path.join(ed, f"{n}.mat")) for n in _NAMES)
+    return {"decay": float(e["decay"]), "warmup": bool(e["warmup"]), "t": int(e["t"]),
+            "params": (W0, b0.ravel(), W1, b1.ravel())}
 
 
 def load_optim_state(directory: str, meta: dict) -> dict | None:

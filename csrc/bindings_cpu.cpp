@@ -13,6 +13,7 @@
 #include "mlp/augment.h"
 #include "mlp/best.h"
 #include "mlp/clip.h"
+#include "mlp/ema.h"
 #include "mlp/shuffle.h"
 
 namespace py = pybind11;
@@ -161,7 +162,7 @@ PYBIND11_MODULE(_cpu, m) {
       [](py::array_t<double> W1, py::array_t<double> b1, py::array_t<double> W2, py::array_t<double> b2, f64arr X,
          i32arr labels, double lr, double reg, int epochs, int batch, int print_every, bool debug,
          std::string outdir, bool shift, int ckpt_precision, int iter0, py::object optim, py::object rates,
-         double clip_norm, py::object update_log) {
+         double clip_norm, py::object update_log, py::object ema) {
         auto v = view(W1, b1, W2, b2);
         check_x(X, v.P);
         cme::cpu::TrainOpts o;
@@ -205,6 +206,24 @@ PYBIND11_MODULE(_cpu, m) {
         o.clip_norm = clip_norm;
         std::vector<double> ulog;
         if (!update_log.is_none()) o.update_log = &ulog;
+        // ema: None, or (decay, warmup, average, count): the average (float64, H P + H + C H + C, [W1|b1|W2|b2]) and the
+        // one-element float64 count of averaged updates are updated in place (csrc/mlp/ema.h)
+        py::array_t<double> ema_avg, ema_cnt;
+        if (!ema.is_none()) {
+          const py::tuple t = ema.cast<py::tuple>();
+          if (t.size() != 4) throw std::invalid_argument("train: ema = (decay, warmup, average, count)");
+          o.ema_rule.decay = t[0].cast<double>();
+          o.ema_rule.warmup = t[1].cast<bool>() ? 1 : 0;
+          if (!py::isinstance<py::array_t<double>>(t[2]) || !py::isinstance<py::array_t<double>>(t[3]))
+            throw std::invalid_argument("train: a float64 average and count expected");
+          ema_avg = t[2].cast<py::array_t<double>>();
+          ema_cnt = t[3].cast<py::array_t<double>>();
+          const int64_t total = (int64_t)v.H * v.P + v.H + (int64_t)v.C * v.H + v.C;
+          if (ema_avg.size() != total || ema_cnt.size() < 1)
+            throw std::invalid_argument("train: the average must hold every parameter, the count one double");
+          o.ema = mut(ema_avg);
+          o.ema_t = mut(ema_cnt);
+        }
         std::vector<double> losses;
         {
           py::gil_scoped_release r;
@@ -225,7 +244,46 @@ PYBIND11_MODULE(_cpu, m) {
       py::arg("reg"), py::arg("epochs"), py::arg("batch"), py::arg("print_every") = 0, py::arg("debug") = false,
       py::arg("outdir") = "Outputs", py::arg("shift") = true, py::arg("ckpt_precision") = 12,
       py::arg("iter0") = 0, py::arg("optim") = py::none(), py::arg("rates") = py::none(), py::arg("clip_norm") = 0.0,
-      py::arg("update_log") = py::none());
+      py::arg("update_log") = py::none(), py::arg("ema") = py::none());
+
+  // the exponential moving average of the parameters (csrc/mlp/ema.h, the header the kernel compiles) on float32 or
+  // float64 arrays: ema_step folds params into ema in place as update t (0-based) and returns t + 1; ema_decay is the
+  // decay d_t of that update.
+  m.def(
+      "ema_decay",
+      [](double decay, bool warmup, int64_t t) {
+        const cme::EmaRule r{decay, warmup ? 1 : 0};
+        if (!cme::ema_rule_ok(r)) throw std::invalid_argument("ema_decay: decay must be in [0, 1)");
+        if (t < 0) throw std::invalid_argument("ema_decay: t must be >= 0");
+        return cme::ema_decay(r, (double)t);
+      },
+      py::arg("decay"), py::arg("warmup"), py::arg("t"));
+  m.def(
+      "ema_step",
+      [](py::array ema, py::array params, double decay, bool warmup, int64_t t) {
+        const cme::EmaRule r{decay, warmup ? 1 : 0};
+        if (!cme::ema_rule_ok(r)) throw std::invalid_argument("ema_step: decay must be in [0, 1)");
+        if (t < 0) throw std::invalid_argument("ema_step: t must be >= 0");
+        const bool f32 = ema.dtype().is(py::dtype::of<float>());
+        if (!f32 && !ema.dtype().is(py::dtype::of<double>()))
+          throw std::invalid_argument("ema_step: float32 or float64 arrays expected");
+        if (!params.dtype().is(ema.dtype()) || params.size() != ema.size() || !(ema.flags() & py::array::c_style) ||
+            !(params.flags() & py::array::c_style) || !ema.writeable())
+          throw std::invalid_argument("ema_step: arrays of one dtype and size, C-contiguous, a writable average expected");
+        const double d = cme::ema_decay(r, (double)t);
+        const py::ssize_t n = ema.size();
+        auto run = [&](auto tag) {
+          using T = decltype(tag);
+          T* e = static_cast<T*>(ema.mutable_data());
+          const T* p = static_cast<const T*>(params.data());
+          const T omd = cme::ema_omd<T>(d);
+          for (py::ssize_t i = 0; i < n; ++i) e[i] = cme::ema_update<T>(e[i], p[i], omd);
+        };
+        if (f32) run(float{});
+        else run(double{});
+        return t + 1;
+      },
+      py::arg("ema"), py::arg("params"), py::arg("decay"), py::arg("warmup"), py::arg("t"));
 
   // one update of the stateful rules (csrc/mlp/optim.h, the header the kernel compiles) on float32 or float64 arrays,
   // in place: kind 0 = momentum / Nesterov (s1 = v), 1 = adam (s1 = m, s2 = s), 2 = the stateless sgd rule (s1 = None:

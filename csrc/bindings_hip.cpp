@@ -16,6 +16,7 @@
 #include "mlp/mlp_step.h"
 #include "mlp/best.h"
 #include "mlp/clip.h"
+#include "mlp/ema.h"
 #include "mlp/optim.h"
 #include "mlp/augment.h"
 #include "mlp/shuffle.h"
@@ -403,6 +404,21 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
         cme::mlp_best_pack(P<const unsigned long long>(slot), P<double>(rows), R, rank, P<void>(s));
       },
       py::arg("slot"), py::arg("rows"), py::arg("R"), py::arg("rank"), py::arg("stream") = 0);
+  // the exponential moving average of the parameters (csrc/mlp/ema.h): one launch behind every applied update; rec =
+  // ema_grid(count) records of 4 doubles; status (the parameter dtype) and err (int32) are the optional skip words
+  m.def("ema_grid", &cme::ema_grid, py::arg("count"));
+  m.def(
+      "mlp_ema_step",
+      [](int dt, double decay, int warmup, uintptr_t params, uintptr_t ema, int64_t count, uintptr_t rec, int nrec,
+         uintptr_t status, uintptr_t err, uintptr_t s) {
+        cme::EmaArgs a;
+        a.dtype = dt; a.rule.decay = decay; a.rule.warmup = warmup;
+        a.params = P<const void>(params); a.ema = P<void>(ema); a.count = count; a.rec = P<double>(rec);
+        a.nrec = nrec; a.status = P<const void>(status); a.err = P<const int32_t>(err);
+        cme::mlp_ema_step(a, P<void>(s));
+      },
+      py::arg("dt"), py::arg("decay"), py::arg("warmup"), py::arg("params"), py::arg("ema"), py::arg("count"),
+      py::arg("rec"), py::arg("nrec"), py::arg("status") = 0, py::arg("err") = 0, py::arg("stream") = 0);
 
   bind_suite(m);
   bind_comm(m);

@@ -184,6 +184,8 @@ std::vector<double> train(NetView net, const double* X, const int* labels, int N
   if (o.rates && o.nrates < (int64_t)o.epochs * ((N + B - 1) / B))
     throw std::invalid_argument("train: the rate table must hold one rate per update of the call");
   if (!(o.clip_norm >= 0.0)) throw std::invalid_argument("train: clip_norm must be >= 0");
+  if (o.ema && (!o.ema_t || !ema_rule_ok(o.ema_rule)))
+    throw std::invalid_argument("train: the average needs its update count and a decay in [0, 1)");
   std::vector<double> flat(o.clip_norm > 0.0 ? total : 0), partials(kClipMaxGrid);
   int64_t upd = 0;
   std::vector<double> a1((size_t)B * H), yc((size_t)B * C);
@@ -263,6 +265,15 @@ std::vector<double> train(NetView net, const double* X, const int* labels, int N
               adam_update(prm[q][i], o.s1[base + i], o.s2[base + i], grd[q][i], k);
           }
         }
+      }
+      if (o.ema) {  // the average follows every update (mlp/ema.h)
+        const double omd = ema_omd<double>(ema_decay(o.ema_rule, *o.ema_t));
+        const double* prm[4] = {net.W1, net.b1, net.W2, net.b2};
+        const int64_t cnt[4] = {H64 * P64, H64, C64 * H64, C64};
+        int64_t base = 0;
+        for (int q = 0; q < 4; base += cnt[q], ++q)
+          for (int64_t i = 0; i < cnt[q]; ++i) o.ema[base + i] = ema_update(o.ema[base + i], prm[q][i], omd);
+        *o.ema_t += 1.0;
       }
       const bool print_flag = o.print_every <= 0 ? batch == 0 : iter % o.print_every == 0;
       if (o.debug && print_flag) {

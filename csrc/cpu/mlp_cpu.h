@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "mlp/ema.h"
 #include "mlp/optim.h"
 
 namespace cme::cpu {
@@ -70,6 +71,11 @@ struct TrainOpts {
   int64_t nrates = 0;
   double clip_norm = 0.0;
   std::vector<double>* update_log = nullptr;
+  // an exponential moving average of the parameters (mlp/ema.h; null: none): ema holds H P + H + C H + C doubles in
+  // the order [W1|b1|W2|b2] and follows every update; *ema_t counts the averaged updates.  Both are carried in and out.
+  EmaRule ema_rule{};
+  double* ema = nullptr;
+  double* ema_t = nullptr;
 };
 
 // Minibatch SGD (neural_network.cpp:219-279): ceil(N/B) batches per epoch, the
