@@ -344,26 +344,17 @@ class MlpEngine:
         epoch_shifts(N, aug.seed, key, ...)[perm[i]].  The shift belongs to the source sample, so the order does not
         change it.  Never composed with the previous state.  On the hip backend one launch of the augmenting gather
         (csrc/mlp/augment.hip) on the current stream: no sync, no read-back, and the buffers keep their addresses."""
-        if self.X is None:
-            raise RuntimeError("load_dataset() first")
-        if self.X0 is None:
-            raise RuntimeError("no pristine copy of the training set: load_dataset(..., keep_source=True) first")
         key, seed = int(key), 0 if shuffle_seed is None else int(shuffle_seed)
-        if not (0 <= seed < 1 << 32 and 0 <= key < 1 << 32):
-            raise ValueError("shuffle seed and key must be in [0, 2^32)")
+        ready = self._gather_ready(seed, key)
         N, P = self.num_samples, self.P
         h, w = aug.shape(P)
-        if N == 0:
+        if not ready:
             return
         if self._shifts is None:
             self._shifts = torch.zeros(N, 2, dtype=torch.int32, device=self.device)
         if self.backend == "hip":
-            ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
-            hip().mlp_augment(ptr(self.X0), ptr(self.labels0), ptr(self.X), ptr(self.labels), ptr(self.XT),
-                              ptr(self.Xs), ptr(self.Xw), ptr(self.XTw), ptr(self._perm), ptr(self._shifts), N, P,
-                              self.X.element_size(), h, w, aug.max_dx, aug.max_dy, aug.seed, key,
-                              int(shuffle_seed is not None), seed,
-                              torch.cuda.current_stream(self.device).cuda_stream)
+            self._gather_launch(hip().mlp_augment, self._shifts.data_ptr(), N, P, self.X.element_size(), h, w,
+                                aug.max_dx, aug.max_dy, aug.seed, key, int(shuffle_seed is not None), seed)
             self.augment_launches += 1
             return
         with torch.no_grad():
@@ -408,24 +399,32 @@ class MlpEngine:
             raise RuntimeError("load_dataset() first")
         return torch.arange(self.num_samples, dtype=torch.int32, device=self.device)
 
-    def _shuffle(self, seed: int, key: int, identity: bool) -> None:
+    def _gather_ready(self, seed: int, key: int) -> bool:
+        """What the shuffle and the augmentation need before they rewrite the resident set; False: the set is empty,
+        there is nothing to do."""
         if self.X is None:
             raise RuntimeError("load_dataset() first")
         if self.X0 is None:
             raise RuntimeError("no pristine copy of the training set: load_dataset(..., keep_source=True) first")
         if not (0 <= seed < 1 << 32 and 0 <= key < 1 << 32):
             raise ValueError("shuffle seed and key must be in [0, 2^32)")
-        N, P = self.num_samples, self.P
-        if N == 0:
+        return self.num_samples != 0
+
+    def _gather_launch(self, launch, *rest) -> None:
+        """hip().mlp_shuffle / mlp_augment on the current stream: the pristine source, the resident layouts and the
+        order as device addresses (0: a layout this engine does not hold), then ``rest``."""
+        held = (self.X0, self.labels0, self.X, self.labels, self.XT, self.Xs, self.Xw, self.XTw, self._perm)
+        launch(*(t.data_ptr() if t is not None else 0 for t in held), *rest,
+               stream=torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _shuffle(self, seed: int, key: int, identity: bool) -> None:
+        if not self._gather_ready(seed, key):
             return
+        N, P = self.num_samples, self.P
         if self._shifts is not None:  # (only after an augmentation: the plain gather restores the loaded pixels)
             self._shifts.zero_()
         if self.backend == "hip":
-            ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
-            hip().mlp_shuffle(ptr(self.X0), ptr(self.labels0), ptr(self.X), ptr(self.labels), ptr(self.XT),
-                              ptr(self.Xs), ptr(self.Xw), ptr(self.XTw), ptr(self._perm), N, P,
-                              self.X.element_size(), seed, key, int(identity),
-                              torch.cuda.current_stream(self.device).cuda_stream)
+            self._gather_launch(hip().mlp_shuffle, N, P, self.X.element_size(), seed, key, int(identity))
             self.shuffle_launches += 1
             return
         with torch.no_grad():

@@ -76,6 +76,18 @@ py::dict form_dict(const cme::StepForm& p) {
       "planes_left_stale"_a = int(p.planes_left_stale));
 }
 
+// what mlp_shuffle and mlp_augment share (csrc/mlp/shuffle.h ShuffleArgs): the source, the six layouts and perm as
+// device addresses, the shapes and the order
+cme::ShuffleArgs gather_args(uintptr_t X0, uintptr_t labels0, uintptr_t X, uintptr_t labels, uintptr_t XT,
+                             uintptr_t Xs, uintptr_t Xw, uintptr_t XTw, uintptr_t perm, int N, int Pd, int es,
+                             uint64_t key, int identity) {
+  cme::ShuffleArgs a;
+  a.X0 = P<const void>(X0); a.labels0 = P<const int>(labels0); a.X = P<void>(X); a.labels = P<int>(labels);
+  a.XT = P<void>(XT); a.Xs = P<void>(Xs); a.Xw = P<void>(Xw); a.XTw = P<void>(XTw); a.perm = P<int>(perm);
+  a.N = N; a.P = Pd; a.es = es; a.key = key; a.identity = identity;
+  return a;
+}
+
 }  // namespace
 
 void bind_suite(py::module_& m);  // suite_bindings.cpp
@@ -290,11 +302,9 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       "mlp_shuffle",
       [](uintptr_t X0, uintptr_t labels0, uintptr_t X, uintptr_t labels, uintptr_t XT, uintptr_t Xs, uintptr_t Xw,
          uintptr_t XTw, uintptr_t perm, int N, int Pd, int es, uint32_t seed, uint32_t key, int identity, uintptr_t s) {
-        cme::ShuffleArgs a;
-        a.X0 = P<const void>(X0); a.labels0 = P<const int>(labels0); a.X = P<void>(X); a.labels = P<int>(labels);
-        a.XT = P<void>(XT); a.Xs = P<void>(Xs); a.Xw = P<void>(Xw); a.XTw = P<void>(XTw); a.perm = P<int>(perm);
-        a.N = N; a.P = Pd; a.es = es; a.key = cme::shuffle_key(seed, key); a.identity = identity;
-        cme::mlp_shuffle(a, P<void>(s));
+        cme::mlp_shuffle(gather_args(X0, labels0, X, labels, XT, Xs, Xw, XTw, perm, N, Pd, es,
+                                     cme::shuffle_key(seed, key), identity),
+                         P<void>(s));
       },
       py::arg("X0"), py::arg("labels0"), py::arg("X"), py::arg("labels"), py::arg("XT"), py::arg("Xs"), py::arg("Xw"),
       py::arg("XTw"), py::arg("perm"), py::arg("N"), py::arg("P"), py::arg("es"), py::arg("seed"), py::arg("key"),
@@ -307,10 +317,8 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
          uintptr_t XTw, uintptr_t perm, uintptr_t shifts, int N, int Pd, int es, int h, int w, int max_dx, int max_dy,
          uint32_t aug_seed, uint32_t key, int shuffled, uint32_t shuffle_seed, uintptr_t s) {
         cme::AugmentArgs aa;
-        cme::ShuffleArgs& a = aa.base;
-        a.X0 = P<const void>(X0); a.labels0 = P<const int>(labels0); a.X = P<void>(X); a.labels = P<int>(labels);
-        a.XT = P<void>(XT); a.Xs = P<void>(Xs); a.Xw = P<void>(Xw); a.XTw = P<void>(XTw); a.perm = P<int>(perm);
-        a.N = N; a.P = Pd; a.es = es; a.key = cme::shuffle_key(shuffle_seed, key); a.identity = shuffled ? 0 : 1;
+        aa.base = gather_args(X0, labels0, X, labels, XT, Xs, Xw, XTw, perm, N, Pd, es,
+                              cme::shuffle_key(shuffle_seed, key), shuffled ? 0 : 1);
         aa.h = h; aa.w = w; aa.max_dx = max_dx; aa.max_dy = max_dy; aa.akey = cme::augment_key(aug_seed, key);
         aa.shifts = P<int>(shifts);
         cme::mlp_augment(aa, P<void>(s));
