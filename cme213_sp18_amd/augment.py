@@ -1,10 +1,16 @@
-"""Augmentation of the resident training set: random shifts per epoch.
+"""Augmentation of the resident training set: random shifts, and random affine maps, per epoch.
 
 ``Shift`` describes the policy the trainers take as ``augment=``: before every epoch each training image is moved by
 its own ``(dx, dy)``, ``|dx| <= max_dx`` and ``|dy| <= max_dy``, and the pixels moved in from outside are zeros.  The
 shift of a sample depends on ``(seed, iteration counter at the epoch start, loaded sample index)`` alone
 (csrc/mlp/augment.h -- the one header the gather kernel csrc/mlp/augment.hip and the host compile), so a re-run epoch
 or a resumed run reproduces it, the shuffle's order does not change it, and every rank forms the same pixels.
+
+``Affine`` adds a small rotation, scaling and shear per image and epoch (csrc/mlp/affine.h, the header of the gather
+kernel csrc/mlp/affine.hip): a table of Q16 inverse maps is built once on the host from the policy's fields, a second
+keyed hash picks each sample's entry, and every destination pixel is a bilinear blend of four source taps -- integers
+for uint8 pixels, one fixed fp64 chain for float elements.  Its shifts are ``Shift``'s, so an ``Affine`` with identity
+transforms is bitwise a ``Shift``.
 """
 from __future__ import annotations
 
@@ -72,7 +78,95 @@ class Shift:
         return f"Shift(max_dx={self.max_dx}, max_dy={self.max_dy}{shape}, seed={self.seed})"
 
 
-def epoch_shifts(n: int, aug: Shift, key: int) -> np.ndarray:
+class Affine:
+    """rotate / shear: the bounds in degrees of the uniform angle per image; scale: a factor or a (lo, hi) range;
+    max_dx, max_dy, height, width, seed: as for ``Shift``; table: the number of distinct transforms."""
+
+    def __init__(self, rotate: float = 15.0, scale=(0.9, 1.1), shear: float = 0.0, max_dx: int = 0,
+                 max_dy: int | None = None, height: int | None = None, width: int | None = None, seed: int = 0,
+                 table: int = 1024):
+        self.rotate, self.shear = float(rotate), float(shear)
+        lo, hi = scale if isinstance(scale, (tuple, list)) else (scale, scale)
+        self.scale = (float(lo), float(hi))
+        self.table_size = int(table)
+        # the shifts, the image shape and the seed are a Shift's (validated there)
+        self._shift = Shift(max_dx, max_dy, height, width, seed)
+        if not 0.0 <= self.rotate <= 180.0:
+            raise ValueError("Affine: rotate must be in [0, 180] degrees")
+        if not 0.0 <= self.shear <= 60.0:
+            raise ValueError("Affine: shear must be in [0, 60] degrees")
+        if not 1.0 / 16 <= self.scale[0] <= self.scale[1] <= 16.0:
+            raise ValueError("Affine: scale must satisfy 1/16 <= lo <= hi <= 16")
+        if not 1 <= self.table_size <= 65536:
+            raise ValueError("Affine: table must be in [1, 65536]")
+        self._table = None
+
+    max_dx = property(lambda self: self._shift.max_dx)
+    max_dy = property(lambda self: self._shift.max_dy)
+    height = property(lambda self: self._shift.height)
+    width = property(lambda self: self._shift.width)
+    seed = property(lambda self: self._shift.seed)
+
+    def shape(self, P: int) -> tuple[int, int]:
+        """(height, width) of the images of an engine with P input features; raises when they do not fit."""
+        h, w = self._shift.shape(P)
+        if max(h, w) > 1 << 24:
+            raise ValueError("Affine: the image sides must be <= 2^24")
+        return h, w
+
+    def table(self) -> np.ndarray:
+        """int32 [table][4]: the Q16 inverse maps {q00, q01, q10, q11}, a pure function of this policy's fields."""
+        if self._table is None:
+            from ._native import cpu
+
+            self._table = cpu().affine_table(self.seed, self.table_size, self.rotate, self.scale[0], self.scale[1],
+                                             self.shear)
+            self._table.setflags(write=False)
+        return self._table
+
+    def table_checksum(self) -> int:
+        """A 64-bit FNV-1a checksum of the table's little-endian bytes (meta.json: the table goes through libm)."""
+        h = 0xcbf29ce484222325
+        for b in self.table().astype("<i4").tobytes():
+            h = ((h ^ b) * 0x100000001b3) & 0xffffffffffffffff
+        return h
+
+    def to_meta(self) -> dict:
+        return {"kind": "affine", "rotate": self.rotate, "scale": list(self.scale), "shear": self.shear,
+                "max_dx": self.max_dx, "max_dy": self.max_dy, "height": self.height, "width": self.width,
+                "seed": self.seed, "table": self.table_size}
+
+    @classmethod
+    def from_meta(cls, meta: dict | None) -> "Affine | None":
+        if meta is None:
+            return None
+        if meta.get("kind") != "affine":
+            raise ValueError(f"unknown augmentation {meta.get('kind')!r}")
+        return cls(meta["rotate"], tuple(meta["scale"]), meta["shear"], meta["max_dx"], meta.get("max_dy"),
+                   meta.get("height"), meta.get("width"), meta.get("seed", 0), meta.get("table", 1024))
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Affine) and self.to_meta() == other.to_meta()
+
+    def __repr__(self) -> str:
+        shape = "" if self.height is None else f", height={self.height}, width={self.width}"
+        return (f"Affine(rotate={self.rotate}, scale={self.scale}, shear={self.shear}, max_dx={self.max_dx}, "
+                f"max_dy={self.max_dy}{shape}, seed={self.seed}, table={self.table_size})")
+
+
+def from_meta(meta: dict | None):
+    """The policy a ``to_meta()`` dict describes (``Shift`` or ``Affine``, by its ``kind``), or None."""
+    if meta is None:
+        return None
+    kind = meta.get("kind", "shift")
+    if kind == "shift":
+        return Shift.from_meta(meta)
+    if kind == "affine":
+        return Affine.from_meta(meta)
+    raise ValueError(f"unknown augmentation {kind!r}")
+
+
+def epoch_shifts(n: int, aug, key: int) -> np.ndarray:
     """int32 [n][2]: (dx, dy) of LOADED sample i in the epoch that starts at iteration counter ``key``."""
     from ._native import cpu
 
@@ -85,3 +179,27 @@ def apply_shifts(x, shifts, h: int, w: int) -> np.ndarray:
     from ._native import cpu
 
     return cpu().augment_rows(np.ascontiguousarray(x), np.ascontiguousarray(shifts, dtype=np.int32), int(h), int(w))
+
+
+def epoch_transforms(n: int, aug: Affine, key: int) -> np.ndarray:
+    """int32 [n]: the table index of LOADED sample i in the epoch that starts at iteration counter ``key``."""
+    from ._native import cpu
+
+    return cpu().epoch_transforms(int(n), aug.seed, int(key), aug.table_size)
+
+
+_KINDS = {"uint8": 0, "float32": 2, "float64": 3}
+
+
+def apply_affine(x, shifts, entries, h: int, w: int) -> np.ndarray:
+    """Rows of h x w images ([N][h * w]; uint8, float32, float64, or bf16 as 2-byte integers), row i resampled through
+    ``entries[i] = (q00, q01, q10, q11)`` (a row of ``Affine.table()``) and moved by ``shifts[i] = (dx, dy)``: the
+    host's form of the rule of csrc/mlp/affine.h."""
+    from ._native import cpu
+
+    x = np.ascontiguousarray(x)
+    kind = _KINDS.get(x.dtype.name, 1 if x.dtype.itemsize == 2 and x.dtype.kind in "iu" else None)
+    if kind is None:
+        raise ValueError(f"apply_affine: elements must be uint8, float32, float64 or bf16 bits, got {x.dtype}")
+    return cpu().affine_rows(x, np.ascontiguousarray(shifts, dtype=np.int32),
+                             np.ascontiguousarray(entries, dtype=np.int32), int(h), int(w), kind)

@@ -53,6 +53,10 @@ class TrainConfig:
     augment_shift: int | None = None    # --augment-shift M: move every training image by up to M pixels per epoch
     augment_shift_y: int | None = None  # --augment-shift-y: the vertical bound (default: M)
     augment_seed: int = 0       # --augment-seed S
+    augment_rotate: float | None = None  # --augment-rotate DEG: rotate every training image by up to DEG per epoch
+    augment_scale: str = ""     # --augment-scale LO[:HI]: scale it by a factor in [LO, HI]
+    augment_shear: float | None = None   # --augment-shear DEG: shear it by up to DEG
+    augment_table: int = 1024   # --augment-table T: the number of distinct transforms (augment.Affine)
     image_shape: str = ""       # --image-shape HxW: the images' rows x columns (default: 28x28, the square of 784)
     gpus: int = 0               # ranks (one per GPU); 0 = WORLD_SIZE of the launcher, else 1.  N > 1 without a
                                 # launcher: the CLI starts the N ranks itself (parallel/launcher.self_launch)
@@ -103,15 +107,27 @@ class TrainConfig:
 
     @property
     def augment(self):
-        """The augment.Shift of the --augment-* flags, or None."""
-        from .augment import Shift
+        """The augment.Shift of the --augment-* flags -- with a transform flag (--augment-rotate / -scale / -shear) the
+        augment.Affine -- or None."""
+        from .augment import Affine, Shift
 
-        if self.augment_shift is None:
+        if self.augment_shift is None and not self.augment_affine:
             return None
         h, w = parse_image_shape(self.image_shape) if self.image_shape else (None, None)
+        if self.augment_affine:
+            aug = Affine(self.augment_rotate or 0.0, parse_scale(self.augment_scale) if self.augment_scale else 1.0,
+                         self.augment_shear or 0.0, self.augment_shift or 0, self.augment_shift_y, h, w,
+                         self.augment_seed, self.augment_table)
+            aug.shape(self.H[0])
+            return aug
         aug = Shift(self.augment_shift, self.augment_shift_y, h, w, self.augment_seed)
         aug.shape(self.H[0])
         return aug
+
+    @property
+    def augment_affine(self) -> bool:
+        """Whether a transform flag makes the policy an augment.Affine."""
+        return self.augment_rotate is not None or bool(self.augment_scale) or self.augment_shear is not None
 
     @property
     def optim(self):
@@ -131,6 +147,18 @@ def parse_image_shape(spec: str) -> tuple[int, int]:
     if len(parts) != 2 or not all(p.isdigit() for p in parts) or int(parts[0]) < 1 or int(parts[1]) < 1:
         raise ValueError(f"--image-shape must be HxW with positive integers (got {spec!r})")
     return int(parts[0]), int(parts[1])
+
+
+def parse_scale(spec: str) -> tuple[float, float]:
+    """'LO' or 'LO:HI' -> (lo, hi)."""
+    parts = spec.split(":")
+    try:
+        vals = [float(p) for p in parts]
+    except ValueError:
+        vals = []
+    if len(vals) not in (1, 2):
+        raise ValueError(f"--augment-scale must be LO or LO:HI (got {spec!r})")
+    return vals[0], vals[-1]
 
 
 # fpcode/main.cpp:113-152 -- "DO NOT change the following parameters"
@@ -210,6 +238,15 @@ def build_parser() -> argparse.ArgumentParser:
                          "default: no augmentation")
     ap.add_argument("--augment-shift-y", type=int, help="the vertical bound of --augment-shift (default: M)")
     ap.add_argument("--augment-seed", type=int, help="seed of the shifts (default 0)")
+    ap.add_argument("--augment-rotate", type=float,
+                    help="before every epoch rotate each training image about its centre by its own random angle, "
+                         "|angle| <= DEG (0..180), resampled bilinearly on the device; alone or with --augment-scale / "
+                         "--augment-shear / --augment-shift (any of the three makes the policy an affine one)")
+    ap.add_argument("--augment-scale", help="LO[:HI]: scale each training image by its own factor in [LO, HI] "
+                                            "(1/16 <= LO <= HI <= 16)")
+    ap.add_argument("--augment-shear", type=float, help="shear each training image by up to DEG (0..60) per epoch")
+    ap.add_argument("--augment-table", type=int,
+                    help="the number of distinct transforms the affine policy draws from (default 1024, up to 65536)")
     ap.add_argument("--image-shape", help="HxW: rows x columns of the images, H * W = 784 (default 28x28)")
     ap.add_argument("--optimizer", choices=["sgd", "momentum", "adam"],
                     help="the update rule (default sgd, the reference's w -= lr g); momentum and adam keep their state "
@@ -322,8 +359,11 @@ def parse_config(argv=None) -> TrainConfig:
         ap.error(f"{', '.join(ema_flags)} need(s) --ema DECAY")
     if cfg.use_ema and cfg.restore_best:
         ap.error("--use-ema and --restore-best both choose the final weights: give one of them")
-    if cfg.augment_shift is None and any(k in explicit for k in ("augment_shift_y", "augment_seed", "image_shape")):
+    if cfg.augment_shift is None and not cfg.augment_affine and any(
+            k in explicit for k in ("augment_shift_y", "augment_seed", "image_shape")):
         ap.error("--augment-shift-y, --augment-seed and --image-shape need --augment-shift")
+    if "augment_table" in explicit and not cfg.augment_affine:
+        ap.error("--augment-table needs --augment-rotate, --augment-scale or --augment-shear")
     try:
         cfg.augment  # the image shape and the bounds (augment.Shift validates)
         cfg.optim  # the hyper-parameters' ranges (optim.Optimizer validates)

@@ -136,6 +136,8 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
     ``augment`` (an ``augment.Shift``; the parallel trainers' ``augment=``): one native epoch at a time on
     ``apply_shifts(X[perm_e], shifts_e[perm_e], h, w)``, shifts_e = the keyed shifts of the loaded samples in the epoch
     that starts at that iteration counter (csrc/mlp/augment.h); without ``shuffle_seed`` the order is the loaded one.
+    An ``augment.Affine`` goes through ``apply_affine`` with the samples' table entries instead (csrc/mlp/affine.h):
+    uint8 ``X`` is blended by the integer rule, as the trainers' resident bytes are, anything else in fp64.
 
     ``ema`` (an ``optim.Ema``; the parallel trainer's ``ema=``): after every update the parameters are folded into an
     average by the rule of csrc/mlp/ema.h.  ``ema_state`` -- ``optim.new_ema_state(nn)``: {"t": the count of averaged
@@ -145,6 +147,7 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
     ``grad_check`` runs a numerical gradient check on the first batch (the
     reference's threshold of 1000 made it a no-op; we assert a real bound).
     """
+    X_raw = X if isinstance(X, np.ndarray) and X.dtype == np.uint8 else None  # (an Affine blends bytes as bytes)
     X = _x64(X)
     labels = np.ascontiguousarray(labels, dtype=np.int32)
     if grad_check:
@@ -201,16 +204,21 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
         losses: list[float] = []
         it = int(iter0)
         if augment is not None:
-            from ..augment import apply_shifts, epoch_shifts
+            from ..augment import Affine, apply_affine, apply_shifts, epoch_shifts, epoch_transforms
 
             img_h, img_w = augment.shape(X.shape[1])
+            affine = isinstance(augment, Affine)
         for ep in range(int(epochs)):
             perm = (cpu().epoch_permutation(n, int(shuffle_seed), it) if shuffle_seed is not None
                     else np.arange(n, dtype=np.int32))
             if rates is not None:
                 kw["rates"] = np.ascontiguousarray(rates[ep * nb:(ep + 1) * nb])
             Xe = np.ascontiguousarray(X[perm])
-            if augment is not None:
+            if augment is not None and affine:  # (csrc/mlp/affine.h: the sample's table entry, then its shift)
+                entries = augment.table()[epoch_transforms(n, augment, it)[perm]]
+                Xe = X_raw[perm] if X_raw is not None else Xe
+                Xe = _x64(apply_affine(Xe, epoch_shifts(n, augment, it)[perm], entries, img_h, img_w))
+            elif augment is not None:
                 Xe = apply_shifts(Xe, epoch_shifts(n, augment, it)[perm], img_h, img_w)
             losses += cpu().train(*nn.params, Xe, np.ascontiguousarray(labels[perm]),
                                   float(learning_rate), float(reg), 1, int(batch_size), int(print_every),

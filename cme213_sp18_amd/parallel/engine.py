@@ -152,6 +152,10 @@ class MlpEngine:
         # by the first augmentation, so a run without one holds nothing
         self.augment_launches = 0
         self._shifts = None
+        # the affine gather (enqueue_augment with an augment.Affine): its launches, the table index of every resident
+        # sample and the uploaded table {policy, device int32 [T][4]} -- allocated by prepare_augment / the first use
+        self.affine_launches = 0
+        self._transforms = self._affine_table = None
         self._eval = None  # the resident validation set and its evaluation buffers (load_eval)
         self._normalize = False
         self.xscale = 1.0
@@ -311,7 +315,7 @@ class MlpEngine:
             self.XTw = self.XT.to(torch.bfloat16).contiguous()
         self.labels = torch.as_tensor(np.asarray(labels, dtype=np.int32)).to(self.device).contiguous()
         self.num_samples = int(self.X.shape[0])
-        self.X0 = self.labels0 = self._perm = self._shifts = None
+        self.X0 = self.labels0 = self._perm = self._shifts = self._transforms = None
         if keep_source:
             # the loaded tensors become the (never written) source and the step reads fresh copies: on the CPU the
             # loaded ones may share memory with the caller's arrays, which a shuffle must not rewrite
@@ -343,7 +347,15 @@ class MlpEngine:
         epoch_permutation(N, shuffle_seed, key), or the loaded order without a seed -- shifted by
         epoch_shifts(N, aug.seed, key, ...)[perm[i]].  The shift belongs to the source sample, so the order does not
         change it.  Never composed with the previous state.  On the hip backend one launch of the augmenting gather
-        (csrc/mlp/augment.hip) on the current stream: no sync, no read-back, and the buffers keep their addresses."""
+        (csrc/mlp/augment.hip) on the current stream: no sync, no read-back, and the buffers keep their addresses.
+
+        With an augment.Affine the image is also resampled through table entry epoch_transforms(...)[perm[i]] of
+        aug.table() (csrc/mlp/affine.h) by one launch of the affine gather (csrc/mlp/affine.hip) instead; the table is
+        uploaded on first use (prepare_augment: before a capture begins)."""
+        from ..augment import Affine
+
+        if isinstance(aug, Affine):
+            return self._enqueue_affine(aug, int(key), shuffle_seed)
         key, seed = int(key), 0 if shuffle_seed is None else int(shuffle_seed)
         ready = self._gather_ready(seed, key)
         N, P = self.num_samples, self.P
@@ -352,6 +364,8 @@ class MlpEngine:
             return
         if self._shifts is None:
             self._shifts = torch.zeros(N, 2, dtype=torch.int32, device=self.device)
+        if self._transforms is not None:  # (only after an affine augmentation: this gather takes no transform)
+            self._transforms.zero_()
         if self.backend == "hip":
             self._gather_launch(hip().mlp_augment, self._shifts.data_ptr(), N, P, self.X.element_size(), h, w,
                                 aug.max_dx, aug.max_dy, aug.seed, key, int(shuffle_seed is not None), seed)
@@ -369,6 +383,65 @@ class MlpEngine:
             self.X.copy_(moved)
             self.labels.copy_(self.labels0.index_select(0, self._perm.long()))
             self._rebuild_from_rows()
+
+    def prepare_augment(self, aug) -> None:
+        """What enqueue_augment(aug, ...) would allocate, now: the shifts, and for an augment.Affine the transforms
+        and the table on the device (once per policy; never rewritten).  The trainers call it from load(), so that no
+        allocation and no upload happens inside a capture."""
+        from ..augment import Affine
+
+        if aug is None or self.X is None or self.num_samples == 0:
+            return
+        aug.shape(self.P)
+        N = self.num_samples
+        if self._shifts is None:
+            self._shifts = torch.zeros(N, 2, dtype=torch.int32, device=self.device)
+        if isinstance(aug, Affine):
+            if self._transforms is None:
+                self._transforms = torch.zeros(N, dtype=torch.int32, device=self.device)
+            if self._affine_table is None or self._affine_table[0] != aug:
+                self._affine_table = (aug, torch.from_numpy(aug.table().copy()).to(self.device).contiguous())
+
+    def _enqueue_affine(self, aug, key: int, shuffle_seed: int | None) -> None:
+        seed = 0 if shuffle_seed is None else int(shuffle_seed)
+        ready = self._gather_ready(seed, key)
+        N, P = self.num_samples, self.P
+        h, w = aug.shape(P)
+        if not ready:
+            return
+        self.prepare_augment(aug)
+        kind = {torch.uint8: 0, torch.bfloat16: 1, torch.float32: 2, torch.float64: 3}.get(self.X0.dtype)
+        if kind is None:
+            raise RuntimeError(f"the affine augmentation takes uint8, bf16, f32 or f64 pixels, not {self.X0.dtype}")
+        if self.backend == "hip":
+            table = self._affine_table[1]
+            self._gather_launch(hip().mlp_affine, self._shifts.data_ptr(), self._transforms.data_ptr(),
+                                table.data_ptr(), int(table.shape[0]), kind, N, P, self.X.element_size(), h, w,
+                                aug.max_dx, aug.max_dy, aug.seed, key, int(shuffle_seed is not None), seed)
+            self.affine_launches += 1
+            return
+        with torch.no_grad():
+            perm = (np.arange(N, dtype=np.int32) if shuffle_seed is None else cpu().epoch_permutation(N, seed, key))
+            shifts = cpu().epoch_shifts(N, aug.seed, key, aug.max_dx, aug.max_dy)[perm]
+            index = cpu().epoch_transforms(N, aug.seed, key, aug.table_size)[perm]
+            self._perm.copy_(torch.from_numpy(perm))
+            self._shifts.copy_(torch.from_numpy(shifts))
+            self._transforms.copy_(torch.from_numpy(index))
+            rows = self.X0.index_select(0, self._perm.long())
+            rows = (rows.view(torch.int16) if kind == 1 else rows).cpu().numpy()
+            moved = cpu().affine_rows(rows, shifts, np.ascontiguousarray(aug.table()[index]), h, w, kind)
+            self.X.copy_(torch.from_numpy(moved).view(self.X.dtype))
+            self.labels.copy_(self.labels0.index_select(0, self._perm.long()))
+            self._rebuild_from_rows()
+
+    def transforms(self) -> torch.Tensor:
+        """The current affine augmentation as a device int32 [N]: resident sample i went through table entry
+        transforms()[i] (zeros before any augmentation, and after unshuffle(), a plain shuffle or a Shift)."""
+        if self._transforms is not None:
+            return self._transforms
+        if self.X is None:
+            raise RuntimeError("load_dataset() first")
+        return torch.zeros(self.num_samples, dtype=torch.int32, device=self.device)
 
     def shifts(self) -> torch.Tensor:
         """The current augmentation as a device int32 [N][2]: resident sample i is its source image moved by
@@ -423,6 +496,8 @@ class MlpEngine:
         N, P = self.num_samples, self.P
         if self._shifts is not None:  # (only after an augmentation: the plain gather restores the loaded pixels)
             self._shifts.zero_()
+        if self._transforms is not None:
+            self._transforms.zero_()
         if self.backend == "hip":
             self._gather_launch(hip().mlp_shuffle, N, P, self.X.element_size(), seed, key, int(identity))
             self.shuffle_launches += 1

@@ -28,6 +28,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
+from ..augment import Affine
 from .comm import Communicator, NullComm
 from .engine import MlpEngine
 
@@ -576,6 +577,8 @@ class DataParallelTrainer:
         self.engine.load_dataset(x_train, y_train, normalize=self.normalize,
                                  keep_source=self.shuffle_seed is not None or self.augment is not None)
         self.N = self.engine.num_samples
+        if isinstance(self.augment, Affine):  # its table goes to the device once, here: never inside a capture
+            self.engine.prepare_augment(self.augment)
         self._graphs.clear()
         if self._xgmi_fused is not None:
             self.fused_allreduce = self._check_fused()

@@ -81,10 +81,15 @@ def run(cfg: TrainConfig) -> dict:
         raise SystemExit(2)
     jlog = JsonLog(cfg.log_json, rank)
     try:
-        aug = cfg.augment  # an augment.Shift or None
+        aug = cfg.augment  # an augment.Shift, an augment.Affine or None
+        # what meta.json and the run header record: the policy and, for an Affine, a checksum of its table (the table
+        # goes through libm: another libm must not silently change a resumed run)
+        aug_meta = aug.to_meta() if aug is not None else None
+        if aug_meta is not None and aug_meta["kind"] == "affine":
+            aug_meta["table_checksum"] = f"{aug.table_checksum():016x}"
         jlog({"event": "config", "world": world, "device": str(device), **placement, **{
             k: v for k, v in vars(cfg).items() if isinstance(v, (int, float, str, bool))},
-            "augment": aug.to_meta() if aug is not None else None,
+            "augment": aug_meta,
             "ema": cfg.ema_rule.as_meta() if cfg.ema_rule is not None else None})
         log0(rank, f"Number of processes = {world}")
         log0(rank, f"Device = {device} ({torch.cuda.get_device_name(device) if device.type == 'cuda' else 'cpu'})")
@@ -151,12 +156,17 @@ def run(cfg: TrainConfig) -> dict:
             if meta.get("shuffle_seed") != cfg.shuffle_seed:
                 log0(rank, f"warning: the checkpoint was trained with --shuffle-seed {meta.get('shuffle_seed')}, this "
                            f"run uses {cfg.shuffle_seed}: the epochs' orders do not continue the checkpoint's")
-            from .augment import Shift
+            from .augment import from_meta as augment_from_meta
 
-            if Shift.from_meta(meta.get("augment")) != aug:
+            if augment_from_meta(meta.get("augment")) != aug:
                 log0(rank, f"warning: the checkpoint was trained with augmentation {meta.get('augment')}, this run "
                            f"uses {aug.to_meta() if aug is not None else None}: the epochs' shifts do not continue "
                            "the checkpoint's")
+            elif aug_meta is not None and meta["augment"].get("table_checksum") != aug_meta.get("table_checksum"):
+                log0(rank, f"warning: the checkpoint's transform table has checksum "
+                           f"{meta['augment'].get('table_checksum')}, this run's has "
+                           f"{aug_meta.get('table_checksum')} (another math library?): the epochs' transforms do not "
+                           "continue the checkpoint's")
         else:
             nn = NeuralNetwork(cfg.H)
         seq_nn = nn.copy()
@@ -236,7 +246,7 @@ def run(cfg: TrainConfig) -> dict:
         ckpt_meta = lambda done: {"epochs": done + meta.get("epochs", 0), "lr": cfg.learning_rate, "reg": cfg.reg,
                                   "seed": cfg.seed, "dtype": cfg.dtype, "iter": tr.iter,
                                   "shuffle_seed": cfg.shuffle_seed,
-                                  "augment": aug.to_meta() if aug is not None else None,
+                                  "augment": aug_meta,
                                   **({"optimizer": opt.as_meta()} if opt.stateful else {}),
                                   **({"schedule": sched.as_meta()} if sched is not None else {}),
                                   **({"clip_norm": clip} if clip is not None else {})}

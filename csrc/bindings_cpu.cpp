@@ -10,6 +10,7 @@
 #include "cpu/io.h"
 #include "cpu/mlp_cpu.h"
 #include "cpu/suite_cpu.h"
+#include "mlp/affine.h"
 #include "mlp/augment.h"
 #include "mlp/best.h"
 #include "mlp/clip.h"
@@ -484,6 +485,89 @@ PYBIND11_MODULE(_cpu, m) {
         return out;
       },
       py::arg("x"), py::arg("shifts"), py::arg("h"), py::arg("w"));
+
+  // the affine augmentation (csrc/mlp/affine.h, the header the affine gather compiles).  The table: int32 [T][4], the
+  // Q16 inverse maps {q00, q01, q10, q11}, a pure function of the arguments (fp64 through libm)
+  m.def(
+      "affine_table",
+      [](uint32_t seed, int T, double rotate, double lo, double hi, double shear) {
+        if (T < 1 || T > cme::kAffineMaxTable) throw std::invalid_argument("affine_table: 1 <= T <= 65536");
+        if (!(rotate >= 0.0 && rotate <= 180.0)) throw std::invalid_argument("affine_table: 0 <= rotate <= 180");
+        if (!(shear >= 0.0 && shear <= 60.0)) throw std::invalid_argument("affine_table: 0 <= shear <= 60");
+        if (!(lo >= 1.0 / 16 && lo <= hi && hi <= 16.0))
+          throw std::invalid_argument("affine_table: 1/16 <= lo <= hi <= 16");
+        py::array_t<int32_t> out({(int64_t)T, (int64_t)4});
+        int32_t* o = out.mutable_data();
+        for (int k = 0; k < T; ++k) {
+          const cme::AffineEntry e = cme::affine_table_entry(seed, (uint32_t)k, rotate, lo, hi, shear);
+          o[4 * k] = e.q00, o[4 * k + 1] = e.q01, o[4 * k + 2] = e.q10, o[4 * k + 3] = e.q11;
+        }
+        return out;
+      },
+      py::arg("seed"), py::arg("T"), py::arg("rotate"), py::arg("lo"), py::arg("hi"), py::arg("shear"));
+  // the table index of SOURCE sample i in the epoch that starts at iteration counter `key`
+  m.def(
+      "epoch_transforms",
+      [](int64_t n, uint32_t seed, uint32_t key, int T) {
+        if (n < 0 || n > INT32_MAX) throw std::invalid_argument("epoch_transforms: n must be in [0, 2^31)");
+        if (T < 1 || T > cme::kAffineMaxTable) throw std::invalid_argument("epoch_transforms: 1 <= T <= 65536");
+        py::array_t<int32_t> out(n);
+        int32_t* o = out.mutable_data();
+        const uint64_t k = cme::augment_key(seed, key);
+        for (int64_t i = 0; i < n; ++i) o[i] = (int32_t)cme::affine_index((uint32_t)i, k, (uint32_t)T);
+        return out;
+      },
+      py::arg("n"), py::arg("seed"), py::arg("key"), py::arg("T"));
+  // rows of h x w images, row i resampled through entries[i] = {q00, q01, q10, q11} and moved by shifts[i] = (dx, dy).
+  // kind: 0 uint8, 1 bf16 (as 2-byte integers), 2 float32, 3 float64; -1: by the dtype (a 2-byte element is bf16)
+  m.def(
+      "affine_rows",
+      [](const py::array& x, const i32arr& shifts, const i32arr& entries, int h, int w, int kind) {
+        if (x.ndim() != 2 || !(x.flags() & py::array::c_style))
+          throw std::invalid_argument("affine_rows: x must be a C-contiguous [N][P] array");
+        const int64_t n = x.shape(0), p = x.shape(1), es = x.itemsize();
+        if (kind < 0) {
+          const char dk = x.dtype().kind();
+          kind = es == 1 ? cme::kAffineU8 : es == 2 ? cme::kAffineBf16 : (es == 4 && dk == 'f') ? cme::kAffineF32
+                 : (es == 8 && dk == 'f') ? cme::kAffineF64 : -1;
+        }
+        if (cme::affine_kind_size(kind) != es || es == 0)
+          throw std::invalid_argument("affine_rows: elements must be uint8, bf16 bits, float32 or float64");
+        if (h < 1 || w < 1 || (int64_t)h * w != p) throw std::invalid_argument("affine_rows: h * w must equal P");
+        if (h > cme::kAffineMaxSide || w > cme::kAffineMaxSide)
+          throw std::invalid_argument("affine_rows: h and w must be <= 2^24");
+        if (shifts.ndim() != 2 || shifts.shape(0) != n || shifts.shape(1) != 2)
+          throw std::invalid_argument("affine_rows: shifts must be int32 [N][2]");
+        if (entries.ndim() != 2 || entries.shape(0) != n || entries.shape(1) != 4)
+          throw std::invalid_argument("affine_rows: entries must be int32 [N][4]");
+        const int32_t* sh = shifts.data();
+        const int32_t* en = entries.data();
+        for (int64_t i = 0; i < n; ++i) {
+          if (sh[2 * i] <= -w || sh[2 * i] >= w || sh[2 * i + 1] <= -h || sh[2 * i + 1] >= h)
+            throw std::invalid_argument("affine_rows: a shift must be smaller than the image");
+          for (int j = 0; j < 4; ++j)
+            if (en[4 * i + j] <= -(1 << 23) || en[4 * i + j] >= (1 << 23))
+              throw std::invalid_argument("affine_rows: an entry must be below 2^23 in magnitude");
+        }
+        py::array out(x.dtype(), {n, p});
+        const auto run = [&](auto u) {
+          using U = decltype(u);
+          const U* src = static_cast<const U*>(x.data());
+          U* dst = static_cast<U*>(out.mutable_data());
+          for (int64_t i = 0; i < n; ++i) {
+            const cme::AffineEntry q{en[4 * i], en[4 * i + 1], en[4 * i + 2], en[4 * i + 3]};
+            for (int y = 0; y < h; ++y)
+              for (int xx = 0; xx < w; ++xx)
+                dst[i * p + (int64_t)y * w + xx] = cme::affine_pixel<U>(src + i * p, y, xx, sh[2 * i], sh[2 * i + 1], q, h, w);
+          }
+        };
+        if (es == 1) run(uint8_t{});
+        else if (es == 2) run(uint16_t{});
+        else if (es == 4) run(uint32_t{});
+        else run(uint64_t{});
+        return out;
+      },
+      py::arg("x"), py::arg("shifts"), py::arg("entries"), py::arg("h"), py::arg("w"), py::arg("kind") = -1);
 
   // ---------------------------------------------------------------- I/O
   m.def(

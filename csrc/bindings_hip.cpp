@@ -18,6 +18,7 @@
 #include "mlp/clip.h"
 #include "mlp/ema.h"
 #include "mlp/optim.h"
+#include "mlp/affine.h"
 #include "mlp/augment.h"
 #include "mlp/shuffle.h"
 #include "suite/suite_kernels.h"
@@ -327,6 +328,28 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       py::arg("XTw"), py::arg("perm"), py::arg("shifts"), py::arg("N"), py::arg("P"), py::arg("es"), py::arg("h"),
       py::arg("w"), py::arg("max_dx"), py::arg("max_dy"), py::arg("aug_seed"), py::arg("key"),
       py::arg("shuffled") = 0, py::arg("shuffle_seed") = 0, py::arg("stream") = 0);
+  // the affine gather (csrc/mlp/affine.hip): mlp_augment's arguments, each image resampled through its table entry
+  // (table: int32 [T][4] on the device; kind: 0 uint8, 1 bf16, 2 f32, 3 f64; transforms: int32 [N] or 0)
+  m.def(
+      "mlp_affine",
+      [](uintptr_t X0, uintptr_t labels0, uintptr_t X, uintptr_t labels, uintptr_t XT, uintptr_t Xs, uintptr_t Xw,
+         uintptr_t XTw, uintptr_t perm, uintptr_t shifts, uintptr_t transforms, uintptr_t table, int T, int kind, int N,
+         int Pd, int es, int h, int w, int max_dx, int max_dy, uint32_t aug_seed, uint32_t key, int shuffled,
+         uint32_t shuffle_seed, uintptr_t s) {
+        cme::AffineArgs fa;
+        cme::AugmentArgs& aa = fa.aug;
+        aa.base = gather_args(X0, labels0, X, labels, XT, Xs, Xw, XTw, perm, N, Pd, es,
+                              cme::shuffle_key(shuffle_seed, key), shuffled ? 0 : 1);
+        aa.h = h; aa.w = w; aa.max_dx = max_dx; aa.max_dy = max_dy; aa.akey = cme::augment_key(aug_seed, key);
+        aa.shifts = P<int>(shifts);
+        fa.table = P<const int32_t>(table); fa.T = T; fa.kind = kind; fa.transforms = P<int>(transforms);
+        cme::mlp_affine(fa, P<void>(s));
+      },
+      py::arg("X0"), py::arg("labels0"), py::arg("X"), py::arg("labels"), py::arg("XT"), py::arg("Xs"), py::arg("Xw"),
+      py::arg("XTw"), py::arg("perm"), py::arg("shifts"), py::arg("transforms"), py::arg("table"), py::arg("T"),
+      py::arg("kind"), py::arg("N"), py::arg("P"), py::arg("es"), py::arg("h"), py::arg("w"), py::arg("max_dx"),
+      py::arg("max_dy"), py::arg("aug_seed"), py::arg("key"), py::arg("shuffled") = 0, py::arg("shuffle_seed") = 0,
+      py::arg("stream") = 0);
   m.def("mlp_split_fused_tiles", &cme::mlp_split_fused_tiles, py::arg("P"), py::arg("H"), py::arg("cap"));
   // the stateful optimizer step (csrc/mlp/optim.h): kind 0 = momentum / Nesterov, 1 = adam; rec = optim_grid(count)
   // records of 4 doubles {t, b1^t, b2^t, 0}
