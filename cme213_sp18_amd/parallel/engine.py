@@ -765,7 +765,9 @@ class MlpEngine:
             lab = self.labels[off:off + n].long()
             if with_loss:
                 self.loss_buf.zero_()
-                self.loss_buf[0] = -torch.log(p[torch.arange(n, device=p.device), lab]).sum().float()
+                # log(sum) - (z_label - m), the HIP heads' form (csrc/mlp/head_math.h head_nll): finite where the
+                # label's probability underflows
+                self.loss_buf[0] = (torch.log(e.sum(dim=1)) - z2.gather(1, lab[:, None])[:, 0]).sum().float()
             onehot = torch.zeros_like(p)
             onehot[torch.arange(n, device=p.device), lab] = 1.0
             D = (p - onehot) * scale

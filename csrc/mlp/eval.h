@@ -9,7 +9,7 @@
 //   [3 + label * C + pred]  confusion counts          (uint64; rows are labels, columns are predictions)
 // pred is the first maximum of z2 = W2 a1 + b2 over the classes < C (ties -> the lower class) and
 // nll = log sum_c exp(z2_c - m) - (z2_label - m), m = max_c z2_c: the same number as -log yhat[label] without the
-// log of an underflowed probability.
+// log of an underflowed probability -- the form of the training heads' loss partials too (head_math.h head_nll).
 //
 // One evaluation is one or more chunks enqueued in order on ONE stream; the first (zero = 1) clears the slot, so
 // re-enqueueing into a slot overwrites it.  Counts are integer atomics, the loss is fp64 partials summed in index

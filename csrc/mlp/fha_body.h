@@ -334,7 +334,7 @@ __device__ __forceinline__ bool fha_body(const SplitStepArgs& f, const HeadArgs&
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, d), make_rsrc(h.D),
                                             (cval && cls < C) ? (cls * h.ldd + gcol) * 4 : kOOB, 0, 0);
     if ((!PS || (HK & 2)) && rt == 0 && h.loss_partial) {
-      float lp = (cval && hit) ? -__logf(yh) : 0.f;
+      float lp = (cval && hit) ? head_nll(ssum, z - m) : 0.f;
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) lp += __shfl_xor(lp, o, 64);
       if (cls == 0) ls[col2] = lp;

@@ -37,6 +37,7 @@
 #include "mlp_kernels.h"
 #include "mlp_split.h"
 
+#include "head_math.h"
 #include "mma_tile.h"
 #include "wgrad_epi.h"
 
@@ -68,11 +69,6 @@ template <typename P>
 __device__ __forceinline__ P mc_exp(P x) {
   if constexpr (std::is_same_v<P, float>) return __expf(x);
   else return exp(x);
-}
-template <typename P>
-__device__ __forceinline__ P mc_log(P x) {
-  if constexpr (std::is_same_v<P, float>) return __logf(x);
-  else return log(x);
 }
 template <typename P>
 __device__ __forceinline__ P mc_max(P a, P b) { return a > b ? a : b; }
@@ -190,12 +186,15 @@ __global__ __launch_bounds__(kMcThreads) void head_mc_kernel(HeadArgs a) {
     mo = mc_max<P>(mo, __shfl_xor(mo, 32, 64));
     m = mo;
   }
-  P ssum = P(0);
+  P ssum = P(0), zl = P(0);  // zl: the label's shifted logit, in the lane that holds it (head_nll)
 #pragma unroll
   for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      z[ct][i] = (16 * ct + Tr::row(g, i)) < C ? mc_exp<P>(z[ct][i] - m) : P(0);
+      const int cls = 16 * ct + Tr::row(g, i);
+      const P zm = z[ct][i] - m;
+      zl = cls == lab ? zm : zl;
+      z[ct][i] = cls < C ? mc_exp<P>(zm) : P(0);
       ssum += z[ct][i];
     }
   ssum += __shfl_xor(ssum, 16, 64);
@@ -226,7 +225,7 @@ __global__ __launch_bounds__(kMcThreads) void head_mc_kernel(HeadArgs a) {
       const int cls = 16 * ct + Tr::row(g, i);
       const P yh = z[ct][i] * inv;
       const bool hit = cval && cls == lab;
-      if (hit) lp = -(float)mc_log<P>(yh);
+      if (hit) lp = (float)head_nll(ssum, zl);
       d[ct][i] = (cval && cls < C) ? (yh - (hit ? P(1) : P(0))) * sc : P(0);
     }
   if (w == 0 && first) {

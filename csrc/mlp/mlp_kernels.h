@@ -41,7 +41,7 @@ struct HeadArgs {
   // the H <= 128 all-gather head (fha_body SWZ & 4): dZ1 is stored in the weight-gradient GEMM's fragment order
   // (mma_tile.h w1s_off over [H][cdiv(ldz, 64) pairs]) instead of row-major -- SplitStepArgs::dz_swz
   int dz_swz = 0;
-  float* loss_partial;            // optional: one sum of -log(yhat[label]) per workgroup
+  float* loss_partial;            // optional: one sum of the columns' nll (head_math.h head_nll) per workgroup
   int* pred;                      // predict mode: argmax labels [n]
   void* probs; int ldp;           // probs mode: [C][ldp]
   int shift;                      // 1: max-shifted softmax; 0: reference form (common.cpp:13-18)

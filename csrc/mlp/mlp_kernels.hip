@@ -25,13 +25,6 @@ template <>
 __device__ __forceinline__ double dev_exp<double>(double x) { return exp(x); }
 
 template <typename T>
-__device__ __forceinline__ T dev_log(T x);
-template <>
-__device__ __forceinline__ float dev_log<float>(float x) { return __logf(x); }
-template <>
-__device__ __forceinline__ double dev_log<double>(double x) { return log(x); }
-
-template <typename T>
 __device__ __forceinline__ T sigmoid_(T x) { return T(1) / (T(1) + dev_exp<T>(-x)); }
 template <>
 __device__ __forceinline__ float sigmoid_<float>(float x) { return sigmoid_f32(x); }  // (head_math.h)
@@ -193,10 +186,12 @@ __device__ __forceinline__ void head_block(const HeadArgs& a, const int vb, cons
 #pragma unroll
     for (int c = 1; c < NC; ++c) m = (c < C && z[c] > m) ? z[c] : m;
   }
-  P s = P(0);
+  P s = P(0), zl = P(0);  // zl: the label's shifted logit, for the loss (head_nll)
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
-    z[c] = c < C ? dev_exp<P>(z[c] - m) : P(0);
+    const P zm = z[c] - m;
+    zl = c == lab ? zm : zl;
+    z[c] = c < C ? dev_exp<P>(zm) : P(0);
     s += z[c];
   }
   const P inv = P(1) / s;
@@ -215,12 +210,7 @@ __device__ __forceinline__ void head_block(const HeadArgs& a, const int vb, cons
 
   // ---- train: D = (yhat - onehot) * scale  (fused softmax + cross-entropy gradient)
   float lpart = 0.f;
-  if (a.loss_partial && part == 0 && valid) {
-    P pl = P(0);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) pl = c == lab ? z[c] : pl;
-    lpart = -(float)dev_log<P>(pl);
-  }
+  if (a.loss_partial && part == 0 && valid) lpart = (float)head_nll(s, zl);
   const P sc = P(a.scale);
 #pragma unroll
   for (int c = 0; c < NC; ++c) z[c] = (z[c] - (c == lab ? P(1) : P(0))) * sc;  // D
@@ -391,7 +381,7 @@ __device__ __forceinline__ void head32(const HeadArgs& a, int ct, int t, Head32L
       const int cls = 4 * g + i;
       const float yh = e[i] * inv;
       const bool hit = cval && cls == lab;
-      if (hit) lp = -__logf(yh);
+      if (hit) lp = head_nll(ssum, z[i] - m);
       const float d = (cval && cls < C) ? (yh - (hit ? 1.f : 0.f)) * sc : 0.f;
       dv[i] = d;
       if (cval && cls < C) Dg[(size_t)cls * a.ldd + col] = d;
@@ -642,8 +632,8 @@ __global__ __launch_bounds__(512) void head_wide_kernel(HeadArgs a, int nrb) {
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
       float d;
-      const float y = head_prob_grad(e[c], inv, c == lab, sc, d);  // the fused wide head's arithmetic
-      if (c == lab) lp = -__logf(y);
+      head_prob_grad(e[c], inv, c == lab, sc, d);  // the fused wide head's arithmetic
+      if (c == lab) lp = head_nll(sum, zs[c][t] - m);
       if (!(ok && c < C)) d = 0.f;
       Ds[c][t] = d;
       if (rb == 0 && ok && c < C) static_cast<float*>(a.D)[(size_t)c * a.ldd + col] = d;

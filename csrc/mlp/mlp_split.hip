@@ -709,9 +709,9 @@ __device__ __forceinline__ void wide_head_ag(const SplitStepArgs& a, const RegaA
       const float inv = 1.f / sum, sc = (float)h.scale;
       const bool hit = cls == lab;
       float d;
-      const float y = head_prob_grad(e, inv, hit, sc, d);  // head_wide_kernel's arithmetic (head_math.h)
+      head_prob_grad(e, inv, hit, sc, d);  // head_wide_kernel's arithmetic (head_math.h)
       if (!(ok && cls < C)) d = 0.f;
-      float lp = hit ? -__logf(y) : 0.f;  // one non-zero lane per column: any summation order is exact
+      float lp = hit ? head_nll(sum, z - m) : 0.f;  // one non-zero lane per column: any summation order is exact
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) lp += __shfl_xor(lp, o, 64);
       const bool hooked = a.ag_test_skip == rt && ct == 0;  // test hook: this tile's D never arrives
