@@ -57,6 +57,8 @@ class TrainConfig:
     augment_scale: str = ""     # --augment-scale LO[:HI]: scale it by a factor in [LO, HI]
     augment_shear: float | None = None   # --augment-shear DEG: shear it by up to DEG
     augment_table: int = 1024   # --augment-table T: the number of distinct transforms (augment.Affine)
+    augment_warp: float | None = None    # --augment-warp ALPHA: elastic distortion, nodes moved by up to ALPHA pixels
+    augment_warp_grid: str = ""  # --augment-warp-grid G or GYxGX: the cells per axis of its lattice (augment.Warp)
     image_shape: str = ""       # --image-shape HxW: the images' rows x columns (default: 28x28, the square of 784)
     gpus: int = 0               # ranks (one per GPU); 0 = WORLD_SIZE of the launcher, else 1.  N > 1 without a
                                 # launcher: the CLI starts the N ranks itself (parallel/launcher.self_launch)
@@ -108,12 +110,21 @@ class TrainConfig:
     @property
     def augment(self):
         """The augment.Shift of the --augment-* flags -- with a transform flag (--augment-rotate / -scale / -shear) the
-        augment.Affine -- or None."""
-        from .augment import Affine, Shift
+        augment.Affine, with a warp flag (--augment-warp / --augment-warp-grid) the augment.Warp over that map -- or
+        None."""
+        from .augment import Affine, Shift, Warp
 
-        if self.augment_shift is None and not self.augment_affine:
+        if self.augment_shift is None and not self.augment_affine and not self.augment_elastic:
             return None
         h, w = parse_image_shape(self.image_shape) if self.image_shape else (None, None)
+        if self.augment_elastic:
+            aug = Warp(4.0 if self.augment_warp is None else self.augment_warp,
+                       parse_warp_grid(self.augment_warp_grid) if self.augment_warp_grid else 3,
+                       self.augment_rotate or 0.0, parse_scale(self.augment_scale) if self.augment_scale else 1.0,
+                       self.augment_shear or 0.0, self.augment_shift or 0, self.augment_shift_y, h, w,
+                       self.augment_seed, self.augment_table)
+            aug.shape(self.H[0])
+            return aug
         if self.augment_affine:
             aug = Affine(self.augment_rotate or 0.0, parse_scale(self.augment_scale) if self.augment_scale else 1.0,
                          self.augment_shear or 0.0, self.augment_shift or 0, self.augment_shift_y, h, w,
@@ -128,6 +139,11 @@ class TrainConfig:
     def augment_affine(self) -> bool:
         """Whether a transform flag makes the policy an augment.Affine."""
         return self.augment_rotate is not None or bool(self.augment_scale) or self.augment_shear is not None
+
+    @property
+    def augment_elastic(self) -> bool:
+        """Whether a warp flag makes the policy an augment.Warp."""
+        return self.augment_warp is not None or bool(self.augment_warp_grid)
 
     @property
     def optim(self):
@@ -159,6 +175,14 @@ def parse_scale(spec: str) -> tuple[float, float]:
     if len(vals) not in (1, 2):
         raise ValueError(f"--augment-scale must be LO or LO:HI (got {spec!r})")
     return vals[0], vals[-1]
+
+
+def parse_warp_grid(spec: str):
+    """'G' or 'GYxGX' -> G or (gy, gx)."""
+    parts = spec.lower().split("x")
+    if len(parts) not in (1, 2) or not all(p.strip().isdigit() for p in parts):
+        raise ValueError(f"--augment-warp-grid must be G or GYxGX (got {spec!r})")
+    return int(parts[0]) if len(parts) == 1 else (int(parts[0]), int(parts[1]))
 
 
 # fpcode/main.cpp:113-152 -- "DO NOT change the following parameters"
@@ -247,6 +271,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--augment-shear", type=float, help="shear each training image by up to DEG (0..60) per epoch")
     ap.add_argument("--augment-table", type=int,
                     help="the number of distinct transforms the affine policy draws from (default 1024, up to 65536)")
+    ap.add_argument("--augment-warp", type=float,
+                    help="before every epoch distort each training image elastically: its own smooth random "
+                         "displacement field, control nodes moved by up to ALPHA pixels (0..8), on top of whatever "
+                         "--augment-rotate / -scale / -shear / -shift give")
+    ap.add_argument("--augment-warp-grid",
+                    help="G or GYxGX: the cells per axis (1..5) of the elastic distortion's control lattice (default 3)")
     ap.add_argument("--image-shape", help="HxW: rows x columns of the images, H * W = 784 (default 28x28)")
     ap.add_argument("--optimizer", choices=["sgd", "momentum", "adam"],
                     help="the update rule (default sgd, the reference's w -= lr g); momentum and adam keep their state "
@@ -359,10 +389,10 @@ def parse_config(argv=None) -> TrainConfig:
         ap.error(f"{', '.join(ema_flags)} need(s) --ema DECAY")
     if cfg.use_ema and cfg.restore_best:
         ap.error("--use-ema and --restore-best both choose the final weights: give one of them")
-    if cfg.augment_shift is None and not cfg.augment_affine and any(
+    if cfg.augment_shift is None and not cfg.augment_affine and not cfg.augment_elastic and any(
             k in explicit for k in ("augment_shift_y", "augment_seed", "image_shape")):
         ap.error("--augment-shift-y, --augment-seed and --image-shape need --augment-shift")
-    if "augment_table" in explicit and not cfg.augment_affine:
+    if "augment_table" in explicit and not cfg.augment_affine and not cfg.augment_elastic:
         ap.error("--augment-table needs --augment-rotate, --augment-scale or --augment-shear")
     try:
         cfg.augment  # the image shape and the bounds (augment.Shift validates)

@@ -137,7 +137,8 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
     ``apply_shifts(X[perm_e], shifts_e[perm_e], h, w)``, shifts_e = the keyed shifts of the loaded samples in the epoch
     that starts at that iteration counter (csrc/mlp/augment.h); without ``shuffle_seed`` the order is the loaded one.
     An ``augment.Affine`` goes through ``apply_affine`` with the samples' table entries instead (csrc/mlp/affine.h):
-    uint8 ``X`` is blended by the integer rule, as the trainers' resident bytes are, anything else in fp64.
+    uint8 ``X`` is blended by the integer rule, as the trainers' resident bytes are, anything else in fp64.  An
+    ``augment.Warp`` goes through ``apply_warp`` with the samples' lattice nodes besides (csrc/mlp/warp.h).
 
     ``ema`` (an ``optim.Ema``; the parallel trainer's ``ema=``): after every update the parameters are folded into an
     average by the rule of csrc/mlp/ema.h.  ``ema_state`` -- ``optim.new_ema_state(nn)``: {"t": the count of averaged
@@ -204,10 +205,12 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
         losses: list[float] = []
         it = int(iter0)
         if augment is not None:
-            from ..augment import Affine, apply_affine, apply_shifts, epoch_shifts, epoch_transforms
+            from ..augment import (Affine, Warp, apply_affine, apply_shifts, apply_warp, epoch_nodes, epoch_shifts,
+                                   epoch_transforms)
 
             img_h, img_w = augment.shape(X.shape[1])
-            affine = isinstance(augment, Affine)
+            warp = isinstance(augment, Warp)
+            affine = warp or isinstance(augment, Affine)
         for ep in range(int(epochs)):
             perm = (cpu().epoch_permutation(n, int(shuffle_seed), it) if shuffle_seed is not None
                     else np.arange(n, dtype=np.int32))
@@ -217,7 +220,11 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
             if augment is not None and affine:  # (csrc/mlp/affine.h: the sample's table entry, then its shift)
                 entries = augment.table()[epoch_transforms(n, augment, it)[perm]]
                 Xe = X_raw[perm] if X_raw is not None else Xe
-                Xe = _x64(apply_affine(Xe, epoch_shifts(n, augment, it)[perm], entries, img_h, img_w))
+                if warp:  # (csrc/mlp/warp.h: the affine map with the field of the sample's nodes on top)
+                    Xe = _x64(apply_warp(Xe, epoch_shifts(n, augment, it)[perm], entries,
+                                         epoch_nodes(n, augment, it)[perm], augment, img_h, img_w))
+                else:
+                    Xe = _x64(apply_affine(Xe, epoch_shifts(n, augment, it)[perm], entries, img_h, img_w))
             elif augment is not None:
                 Xe = apply_shifts(Xe, epoch_shifts(n, augment, it)[perm], img_h, img_w)
             losses += cpu().train(*nn.params, Xe, np.ascontiguousarray(labels[perm]),

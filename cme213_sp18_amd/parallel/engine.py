@@ -156,6 +156,10 @@ class MlpEngine:
         # sample and the uploaded table {policy, device int32 [T][4]} -- allocated by prepare_augment / the first use
         self.affine_launches = 0
         self._transforms = self._affine_table = None
+        # the warping gather (enqueue_augment with an augment.Warp): its launches and the uploaded axis tables
+        # {(grid, h, w), device int32 [h + w][5]} -- it shares the shifts, the transforms and the table above
+        self.warp_launches = 0
+        self._warp_axes = None
         self._eval = None  # the resident validation set and its evaluation buffers (load_eval)
         self._normalize = False
         self.xscale = 1.0
@@ -351,9 +355,15 @@ class MlpEngine:
 
         With an augment.Affine the image is also resampled through table entry epoch_transforms(...)[perm[i]] of
         aug.table() (csrc/mlp/affine.h) by one launch of the affine gather (csrc/mlp/affine.hip) instead; the table is
-        uploaded on first use (prepare_augment: before a capture begins)."""
-        from ..augment import Affine
+        uploaded on first use (prepare_augment: before a capture begins).
 
+        With an augment.Warp every source position of that resampling is moved by the field of the sample's lattice
+        epoch_nodes(...)[perm[i]] (csrc/mlp/warp.h) by one launch of the warping gather (csrc/mlp/warp.hip) instead;
+        its axis tables are uploaded next to the table."""
+        from ..augment import Affine, Warp
+
+        if isinstance(aug, Warp):
+            return self._enqueue_warp(aug, int(key), shuffle_seed)
         if isinstance(aug, Affine):
             return self._enqueue_affine(aug, int(key), shuffle_seed)
         key, seed = int(key), 0 if shuffle_seed is None else int(shuffle_seed)
@@ -385,10 +395,11 @@ class MlpEngine:
             self._rebuild_from_rows()
 
     def prepare_augment(self, aug) -> None:
-        """What enqueue_augment(aug, ...) would allocate, now: the shifts, and for an augment.Affine the transforms
-        and the table on the device (once per policy; never rewritten).  The trainers call it from load(), so that no
-        allocation and no upload happens inside a capture."""
-        from ..augment import Affine
+        """What enqueue_augment(aug, ...) would allocate, now: the shifts, for an augment.Affine the transforms and
+        the table on the device, and for an augment.Warp those of its Affine and the axis tables (once per policy;
+        never rewritten).  The trainers call it from load(), so that no allocation and no upload happens inside a
+        capture."""
+        from ..augment import Affine, Warp
 
         if aug is None or self.X is None or self.num_samples == 0:
             return
@@ -401,6 +412,47 @@ class MlpEngine:
                 self._transforms = torch.zeros(N, dtype=torch.int32, device=self.device)
             if self._affine_table is None or self._affine_table[0] != aug:
                 self._affine_table = (aug, torch.from_numpy(aug.table().copy()).to(self.device).contiguous())
+        if isinstance(aug, Warp):
+            self.prepare_augment(aug.affine)
+            h, w = aug.shape(self.P)
+            if self._warp_axes is None or self._warp_axes[0] != (aug.grid, h, w):
+                self._warp_axes = ((aug.grid, h, w),
+                                   torch.from_numpy(aug.axes(h, w).copy()).to(self.device).contiguous())
+
+    def _enqueue_warp(self, aug, key: int, shuffle_seed: int | None) -> None:
+        seed = 0 if shuffle_seed is None else int(shuffle_seed)
+        ready = self._gather_ready(seed, key)
+        N, P = self.num_samples, self.P
+        h, w = aug.shape(P)
+        if not ready:
+            return
+        self.prepare_augment(aug)
+        kind = {torch.uint8: 0, torch.bfloat16: 1, torch.float32: 2, torch.float64: 3}.get(self.X0.dtype)
+        if kind is None:
+            raise RuntimeError(f"the elastic distortion takes uint8, bf16, f32 or f64 pixels, not {self.X0.dtype}")
+        if self.backend == "hip":
+            table, axes = self._affine_table[1], self._warp_axes[1]
+            self._gather_launch(hip().mlp_warp, self._shifts.data_ptr(), self._transforms.data_ptr(),
+                                table.data_ptr(), int(table.shape[0]), kind, axes.data_ptr(), aug.grid[0], aug.grid[1],
+                                aug.bound, N, P, self.X.element_size(), h, w, aug.max_dx, aug.max_dy, aug.seed, key,
+                                int(shuffle_seed is not None), seed)
+            self.warp_launches += 1
+            return
+        with torch.no_grad():
+            perm = (np.arange(N, dtype=np.int32) if shuffle_seed is None else cpu().epoch_permutation(N, seed, key))
+            shifts = cpu().epoch_shifts(N, aug.seed, key, aug.max_dx, aug.max_dy)[perm]
+            index = cpu().epoch_transforms(N, aug.seed, key, aug.table_size)[perm]
+            nodes = np.ascontiguousarray(cpu().epoch_nodes(N, aug.seed, key, aug.nodes, aug.bound)[perm])
+            self._perm.copy_(torch.from_numpy(perm))
+            self._shifts.copy_(torch.from_numpy(shifts))
+            self._transforms.copy_(torch.from_numpy(index))
+            rows = self.X0.index_select(0, self._perm.long())
+            rows = (rows.view(torch.int16) if kind == 1 else rows).cpu().numpy()
+            moved = cpu().warp_rows(rows, shifts, np.ascontiguousarray(aug.table()[index]), nodes, aug.axes(h, w), h,
+                                    w, aug.grid[0], aug.grid[1], kind)
+            self.X.copy_(torch.from_numpy(moved).view(self.X.dtype))
+            self.labels.copy_(self.labels0.index_select(0, self._perm.long()))
+            self._rebuild_from_rows()
 
     def _enqueue_affine(self, aug, key: int, shuffle_seed: int | None) -> None:
         seed = 0 if shuffle_seed is None else int(shuffle_seed)

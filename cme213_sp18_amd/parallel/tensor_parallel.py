@@ -28,7 +28,7 @@ import time
 import numpy as np
 import torch
 
-from ..augment import Affine
+from ..augment import Affine, Warp
 from .comm import Communicator, NullComm
 from .engine import MlpEngine
 from .trainer import EpochPlan, TrainStats
@@ -185,7 +185,7 @@ class TensorParallelTrainer:
         self.engine.load_dataset(x_train, y_train, normalize=self.normalize,
                                  keep_source=self.shuffle_seed is not None or self.augment is not None)
         self.N = self.engine.num_samples
-        if isinstance(self.augment, Affine):  # its table goes to the device once, here: never inside a capture
+        if isinstance(self.augment, (Affine, Warp)):  # its tables go to the device once, here: never inside a capture
             self.engine.prepare_augment(self.augment)
 
     def epoch_plan(self, N: int | None = None) -> EpochPlan:

@@ -28,7 +28,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from ..augment import Affine
+from ..augment import Affine, Warp
 from .comm import Communicator, NullComm
 from .engine import MlpEngine
 
@@ -577,7 +577,7 @@ class DataParallelTrainer:
         self.engine.load_dataset(x_train, y_train, normalize=self.normalize,
                                  keep_source=self.shuffle_seed is not None or self.augment is not None)
         self.N = self.engine.num_samples
-        if isinstance(self.augment, Affine):  # its table goes to the device once, here: never inside a capture
+        if isinstance(self.augment, (Affine, Warp)):  # its tables go to the device once, here: never inside a capture
             self.engine.prepare_augment(self.augment)
         self._graphs.clear()
         if self._xgmi_fused is not None:

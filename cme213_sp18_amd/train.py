@@ -81,12 +81,14 @@ def run(cfg: TrainConfig) -> dict:
         raise SystemExit(2)
     jlog = JsonLog(cfg.log_json, rank)
     try:
-        aug = cfg.augment  # an augment.Shift, an augment.Affine or None
+        aug = cfg.augment  # an augment.Shift, an augment.Affine, an augment.Warp or None
         # what meta.json and the run header record: the policy and, for an Affine, a checksum of its table (the table
         # goes through libm: another libm must not silently change a resumed run)
         aug_meta = aug.to_meta() if aug is not None else None
         if aug_meta is not None and aug_meta["kind"] == "affine":
             aug_meta["table_checksum"] = f"{aug.table_checksum():016x}"
+        elif aug_meta is not None and aug_meta["kind"] == "warp":  # (its axis tables are built in fp64 too)
+            aug_meta["table_checksum"] = f"{aug.table_checksum(*aug.shape(cfg.H[0])):016x}"
         jlog({"event": "config", "world": world, "device": str(device), **placement, **{
             k: v for k, v in vars(cfg).items() if isinstance(v, (int, float, str, bool))},
             "augment": aug_meta,

@@ -16,6 +16,7 @@
 #include "mlp/clip.h"
 #include "mlp/ema.h"
 #include "mlp/shuffle.h"
+#include "mlp/warp.h"
 
 namespace py = pybind11;
 using f64arr = py::array_t<double, py::array::c_style | py::array::forcecast>;
@@ -568,6 +569,165 @@ PYBIND11_MODULE(_cpu, m) {
         return out;
       },
       py::arg("x"), py::arg("shifts"), py::arg("entries"), py::arg("h"), py::arg("w"), py::arg("kind") = -1);
+
+  // the elastic distortion (csrc/mlp/warp.h, the header the warping gather compiles).  The axis tables: int32
+  // [h + w][5] = {i, w0, w1, w2, w3}, the y axis first, a pure function of the arguments
+  m.def(
+      "warp_axes",
+      [](int h, int w, int gy, int gx) {
+        if (h < 1 || w < 1 || h > cme::kAffineMaxSide || w > cme::kAffineMaxSide)
+          throw std::invalid_argument("warp_axes: 1 <= h, w <= 2^24");
+        if (gy < 1 || gy > cme::kWarpMaxGrid || gx < 1 || gx > cme::kWarpMaxGrid)
+          throw std::invalid_argument("warp_axes: 1 <= gy, gx <= 5");
+        py::array_t<int32_t> out({(int64_t)h + w, (int64_t)5});
+        int32_t* o = out.mutable_data();
+        for (int64_t k = 0; k < (int64_t)h + w; ++k) {
+          const cme::WarpAxis e = k < h ? cme::warp_axis_entry((int)k, h, gy) : cme::warp_axis_entry((int)(k - h), w, gx);
+          o[5 * k] = e.i;
+          for (int j = 0; j < 4; ++j) o[5 * k + 1 + j] = e.w[j];
+        }
+        return out;
+      },
+      py::arg("h"), py::arg("w"), py::arg("gy"), py::arg("gx"));
+  // int32 [n][L][2]: (ddx, ddy) in Q8 of node j of SOURCE sample i in the epoch that starts at iteration counter `key`
+  m.def(
+      "epoch_nodes",
+      [](int64_t n, uint32_t seed, uint32_t key, int L, int A) {
+        if (n < 0 || n > INT32_MAX) throw std::invalid_argument("epoch_nodes: n must be in [0, 2^31)");
+        if (L < 1 || L > cme::kWarpMaxNodes) throw std::invalid_argument("epoch_nodes: 1 <= L <= 64");
+        if (A < 0 || A > cme::kWarpMaxA) throw std::invalid_argument("epoch_nodes: 0 <= A <= 2048");
+        py::array_t<int32_t> out({n, (int64_t)L, (int64_t)2});
+        int32_t* o = out.mutable_data();
+        const uint64_t k = cme::augment_key(seed, key);
+        for (int64_t i = 0; i < n; ++i) {
+          const uint64_t nk = cme::warp_node_key((uint32_t)i, k);
+          for (int j = 0; j < L; ++j) {
+            const cme::WarpNode nd = cme::warp_node(nk, (uint32_t)j, A);
+            o[(i * L + j) * 2] = nd.ddx, o[(i * L + j) * 2 + 1] = nd.ddy;
+          }
+        }
+        return out;
+      },
+      py::arg("n"), py::arg("seed"), py::arg("key"), py::arg("L"), py::arg("A"));
+  {
+    // what warp_field and warp_rows share: the axis tables and one sample's or every sample's nodes, range-checked so
+    // that no node index leaves the lattice and no product leaves int32
+    const auto check_axes = [](const char* who, const i32arr& axes, int h, int w, int gy, int gx) {
+      const std::string p = std::string(who) + ": ";
+      if (gy < 1 || gy > cme::kWarpMaxGrid || gx < 1 || gx > cme::kWarpMaxGrid)
+        throw std::invalid_argument(p + "1 <= gy, gx <= 5");
+      if (h < 1 || w < 1 || h > cme::kAffineMaxSide || w > cme::kAffineMaxSide)
+        throw std::invalid_argument(p + "1 <= h, w <= 2^24");
+      if (axes.ndim() != 2 || axes.shape(0) != (int64_t)h + w || axes.shape(1) != 5)
+        throw std::invalid_argument(p + "axes must be int32 [h + w][5]");
+      const int32_t* ax = axes.data();
+      for (int64_t k = 0; k < (int64_t)h + w; ++k) {
+        if (ax[5 * k] < 0 || ax[5 * k] >= (k < h ? gy : gx))
+          throw std::invalid_argument(p + "an axis entry's cell must lie inside the grid");
+        int sum = 0;
+        for (int j = 1; j < 5; ++j) {
+          if (ax[5 * k + j] < 0 || ax[5 * k + j] > cme::kWarpOne)
+            throw std::invalid_argument(p + "an axis weight must be in [0, 4096]");
+          sum += ax[5 * k + j];
+        }
+        if (sum != cme::kWarpOne) throw std::invalid_argument(p + "an axis entry's weights must sum to 4096");
+      }
+    };
+    const auto check_nodes = [](const char* who, const int32_t* nd, int64_t count) {
+      for (int64_t k = 0; k < count; ++k)
+        if (nd[k] < -cme::kWarpMaxA || nd[k] > cme::kWarpMaxA)
+          throw std::invalid_argument(std::string(who) + ": a node must be in [-2048, 2048]");
+    };
+    const auto axis_at = [](const int32_t* ax, int64_t k) {
+      return cme::WarpAxis{ax[5 * k], {ax[5 * k + 1], ax[5 * k + 2], ax[5 * k + 3], ax[5 * k + 4]}};
+    };
+    // int32 [h][w][2]: (d17x, d17y), the displacement of every destination pixel in 2^-17 pixel, of one sample's
+    // nodes int32 [L][2]
+    m.def(
+        "warp_field",
+        [=](const i32arr& nodes, const i32arr& axes, int h, int w, int gy, int gx) {
+          check_axes("warp_field", axes, h, w, gy, gx);
+          const int L = (gy + 3) * (gx + 3);
+          if (nodes.ndim() != 2 || nodes.shape(0) != L || nodes.shape(1) != 2)
+            throw std::invalid_argument("warp_field: nodes must be int32 [(gy + 3)(gx + 3)][2]");
+          const int32_t* nd = nodes.data();
+          check_nodes("warp_field", nd, 2 * (int64_t)L);
+          const int32_t* ax = axes.data();
+          py::array_t<int32_t> out({(int64_t)h, (int64_t)w, (int64_t)2});
+          int32_t* o = out.mutable_data();
+          for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+              const cme::WarpDisp d = cme::warp_displace(axis_at(ax, y), axis_at(ax, (int64_t)h + x), gx, [&](int j) {
+                return cme::WarpNode{nd[2 * j], nd[2 * j + 1]};
+              });
+              o[((int64_t)y * w + x) * 2] = d.x, o[((int64_t)y * w + x) * 2 + 1] = d.y;
+            }
+          return out;
+        },
+        py::arg("nodes"), py::arg("axes"), py::arg("h"), py::arg("w"), py::arg("gy"), py::arg("gx"));
+    // affine_rows with row i's source positions moved by the field of nodes[i] (int32 [N][L][2]); kind as there
+    m.def(
+        "warp_rows",
+        [=](const py::array& x, const i32arr& shifts, const i32arr& entries, const i32arr& nodes, const i32arr& axes,
+            int h, int w, int gy, int gx, int kind) {
+          if (x.ndim() != 2 || !(x.flags() & py::array::c_style))
+            throw std::invalid_argument("warp_rows: x must be a C-contiguous [N][P] array");
+          const int64_t n = x.shape(0), p = x.shape(1), es = x.itemsize();
+          if (kind < 0) {
+            const char dk = x.dtype().kind();
+            kind = es == 1 ? cme::kAffineU8 : es == 2 ? cme::kAffineBf16 : (es == 4 && dk == 'f') ? cme::kAffineF32
+                   : (es == 8 && dk == 'f') ? cme::kAffineF64 : -1;
+          }
+          if (cme::affine_kind_size(kind) != es || es == 0)
+            throw std::invalid_argument("warp_rows: elements must be uint8, bf16 bits, float32 or float64");
+          if (h < 1 || w < 1 || (int64_t)h * w != p) throw std::invalid_argument("warp_rows: h * w must equal P");
+          check_axes("warp_rows", axes, h, w, gy, gx);
+          const int L = (gy + 3) * (gx + 3);
+          if (shifts.ndim() != 2 || shifts.shape(0) != n || shifts.shape(1) != 2)
+            throw std::invalid_argument("warp_rows: shifts must be int32 [N][2]");
+          if (entries.ndim() != 2 || entries.shape(0) != n || entries.shape(1) != 4)
+            throw std::invalid_argument("warp_rows: entries must be int32 [N][4]");
+          if (nodes.ndim() != 3 || nodes.shape(0) != n || nodes.shape(1) != L || nodes.shape(2) != 2)
+            throw std::invalid_argument("warp_rows: nodes must be int32 [N][(gy + 3)(gx + 3)][2]");
+          const int32_t* sh = shifts.data();
+          const int32_t* en = entries.data();
+          const int32_t* nd = nodes.data();
+          const int32_t* ax = axes.data();
+          check_nodes("warp_rows", nd, n * L * 2);
+          for (int64_t i = 0; i < n; ++i) {
+            if (sh[2 * i] <= -w || sh[2 * i] >= w || sh[2 * i + 1] <= -h || sh[2 * i + 1] >= h)
+              throw std::invalid_argument("warp_rows: a shift must be smaller than the image");
+            for (int j = 0; j < 4; ++j)
+              if (en[4 * i + j] <= -(1 << 23) || en[4 * i + j] >= (1 << 23))
+                throw std::invalid_argument("warp_rows: an entry must be below 2^23 in magnitude");
+          }
+          py::array out(x.dtype(), {n, p});
+          const auto run = [&](auto u) {
+            using U = decltype(u);
+            const U* src = static_cast<const U*>(x.data());
+            U* dst = static_cast<U*>(out.mutable_data());
+            for (int64_t i = 0; i < n; ++i) {
+              const cme::AffineEntry q{en[4 * i], en[4 * i + 1], en[4 * i + 2], en[4 * i + 3]};
+              const int32_t* ni = nd + i * L * 2;
+              for (int y = 0; y < h; ++y)
+                for (int xx = 0; xx < w; ++xx) {
+                  const cme::WarpDisp d = cme::warp_displace(axis_at(ax, y), axis_at(ax, (int64_t)h + xx), gx, [&](int j) {
+                    return cme::WarpNode{ni[2 * j], ni[2 * j + 1]};
+                  });
+                  const cme::AffineTaps t = cme::warp_taps(y, xx, sh[2 * i], sh[2 * i + 1], q, h, w, d);
+                  dst[i * p + (int64_t)y * w + xx] = cme::warp_blend<U>(src + i * p, t, h, w);
+                }
+            }
+          };
+          if (es == 1) run(uint8_t{});
+          else if (es == 2) run(uint16_t{});
+          else if (es == 4) run(uint32_t{});
+          else run(uint64_t{});
+          return out;
+        },
+        py::arg("x"), py::arg("shifts"), py::arg("entries"), py::arg("nodes"), py::arg("axes"), py::arg("h"),
+        py::arg("w"), py::arg("gy"), py::arg("gx"), py::arg("kind") = -1);
+  }
 
   // ---------------------------------------------------------------- I/O
   m.def(

@@ -21,6 +21,7 @@
 #include "mlp/affine.h"
 #include "mlp/augment.h"
 #include "mlp/shuffle.h"
+#include "mlp/warp.h"
 #include "suite/suite_kernels.h"
 
 namespace py = pybind11;
@@ -350,6 +351,30 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       py::arg("kind"), py::arg("N"), py::arg("P"), py::arg("es"), py::arg("h"), py::arg("w"), py::arg("max_dx"),
       py::arg("max_dy"), py::arg("aug_seed"), py::arg("key"), py::arg("shuffled") = 0, py::arg("shuffle_seed") = 0,
       py::arg("stream") = 0);
+  // the warping gather (csrc/mlp/warp.hip): mlp_affine's arguments, every source position moved by the sample's own
+  // displacement field (axes: int32 [h + w][5] on the device; gy, gx: cells per axis; A: the nodes' bound in Q8)
+  m.def(
+      "mlp_warp",
+      [](uintptr_t X0, uintptr_t labels0, uintptr_t X, uintptr_t labels, uintptr_t XT, uintptr_t Xs, uintptr_t Xw,
+         uintptr_t XTw, uintptr_t perm, uintptr_t shifts, uintptr_t transforms, uintptr_t table, int T, int kind,
+         uintptr_t axes, int gy, int gx, int A, int N, int Pd, int es, int h, int w, int max_dx, int max_dy,
+         uint32_t aug_seed, uint32_t key, int shuffled, uint32_t shuffle_seed, uintptr_t s) {
+        cme::WarpArgs wa;
+        cme::AffineArgs& fa = wa.aff;
+        cme::AugmentArgs& aa = fa.aug;
+        aa.base = gather_args(X0, labels0, X, labels, XT, Xs, Xw, XTw, perm, N, Pd, es,
+                              cme::shuffle_key(shuffle_seed, key), shuffled ? 0 : 1);
+        aa.h = h; aa.w = w; aa.max_dx = max_dx; aa.max_dy = max_dy; aa.akey = cme::augment_key(aug_seed, key);
+        aa.shifts = P<int>(shifts);
+        fa.table = P<const int32_t>(table); fa.T = T; fa.kind = kind; fa.transforms = P<int>(transforms);
+        wa.axes = P<const int32_t>(axes); wa.gy = gy; wa.gx = gx; wa.A = A;
+        cme::mlp_warp(wa, P<void>(s));
+      },
+      py::arg("X0"), py::arg("labels0"), py::arg("X"), py::arg("labels"), py::arg("XT"), py::arg("Xs"), py::arg("Xw"),
+      py::arg("XTw"), py::arg("perm"), py::arg("shifts"), py::arg("transforms"), py::arg("table"), py::arg("T"),
+      py::arg("kind"), py::arg("axes"), py::arg("gy"), py::arg("gx"), py::arg("A"), py::arg("N"), py::arg("P"),
+      py::arg("es"), py::arg("h"), py::arg("w"), py::arg("max_dx"), py::arg("max_dy"), py::arg("aug_seed"),
+      py::arg("key"), py::arg("shuffled") = 0, py::arg("shuffle_seed") = 0, py::arg("stream") = 0);
   m.def("mlp_split_fused_tiles", &cme::mlp_split_fused_tiles, py::arg("P"), py::arg("H"), py::arg("cap"));
   // the stateful optimizer step (csrc/mlp/optim.h): kind 0 = momentum / Nesterov, 1 = adam; rec = optim_grid(count)
   // records of 4 doubles {t, b1^t, b2^t, 0}
