@@ -64,6 +64,14 @@ def sum_even_odd_gpu(v: torch.Tensor, out: torch.Tensor | None = None) -> torch.
         raise TypeError("sum_even_odd_gpu: need a 32-bit integer tensor")
     if out is None:
         out = torch.empty(2, dtype=torch.int64, device=v.device)
+    else:  # the kernel writes two 64-bit sums through the raw pointer: refuse anything it would overrun
+        require_cuda(out)
+        if out.dtype not in (torch.int64, torch.uint64):
+            raise TypeError("sum_even_odd_gpu: need a 64-bit integer output")
+        if out.device != v.device:
+            raise ValueError("sum_even_odd_gpu: output must be on the input's device")
+        if out.numel() != 2:
+            raise ValueError("sum_even_odd_gpu: output must hold exactly 2 sums")
     kernels().sum_even_odd(v.data_ptr(), v.numel(), out.data_ptr(), stream_handle())
     return out
 

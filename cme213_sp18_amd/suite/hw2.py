@@ -44,6 +44,16 @@ def shift_gpu(inp: torch.Tensor, shift: int, width: int = 16, out: torch.Tensor 
         raise ValueError("shift_gpu: input must be aligned to the lane width")
     if out is None:
         out = torch.empty_like(inp)
+    else:  # the kernel writes inp.numel() bytes through the raw pointer: refuse anything it would overrun
+        require_cuda(out)
+        if out.dtype != torch.uint8:
+            raise TypeError("shift_gpu: uint8 output")
+        if out.device != inp.device:
+            raise ValueError("shift_gpu: output must be on the input's device")
+        if out.numel() != inp.numel():
+            raise ValueError("shift_gpu: output must have the input's size")
+        if width > 1 and out.data_ptr() % width:
+            raise ValueError("shift_gpu: output must be aligned to the lane width")
     kernels().shift_bytes(inp.data_ptr(), out.data_ptr(), inp.numel(), shift & 255, width, block, grid_cap,
                           stream_handle())
     return out

@@ -186,7 +186,8 @@ __device__ __forceinline__ f32x4 ld4p(__amdgpu_buffer_rsrc_t r, int64_t elem) {
 // same time (both at the start, or both at the end), so one of the two reads of each halo row hits L2 (the
 // neighbouring workgroup is blockIdx + nbx: the same XCD whenever nbx % 8 == 0, e.g. 12288-wide grids).  The window
 // is indexed by grid offset (win[B + dir * k] is row center + k), so every output is the same sum in the same order:
-// bitwise the one-direction kernel.
+// bitwise the one-direction kernel (tests/test_gpu_suite_edges.py: every stencil_lds_tune case against the production
+// walk on a noise field).
 template <int ORDER, int ROWS, int AHEAD = kLdsAhead, int CP = 0, int DIR = 1, bool NTST = true>
 __device__ __forceinline__ void stencil_lds_walk(float* __restrict__ next, const float* __restrict__ curr, int gx,
                                                  int gy, int nx, int ny, float xcfl, float ycfl, int bx, int by,
@@ -297,7 +298,8 @@ __device__ __forceinline__ void stencil_lds_body(float* __restrict__ next, const
 // launch forms them -- and pushes it into a 9-row u1 window; once that is full, stage 2 forms u2 of ITS centre row.
 // The x-neighbours of both stages come from the wave's LDS rows (u0 with the strip's halo float4s; u1 needs none).
 // A block of ROWS output rows reads ROWS + 16 u0 rows (the halo of both steps).  Every value is the same expression
-// on the same operands as in two one-step launches: bitwise those (tests/test_gpu_suite.py).
+// on the same operands as in two one-step launches: bitwise those (tests/test_suite_gpu.py on the smooth field at the
+// automatic rows; tests/test_gpu_suite_edges.py on noise at every (rows, ahead) of stencil_step2_bc's switch).
 template <int ORDER, int ROWS, int AHEAD = kLdsAhead>
 __device__ __forceinline__ void stencil_lds2_walk(float* __restrict__ next, const float* __restrict__ curr, int gx,
                                                   int gy, int nx, int ny, float xcfl, float ycfl, float scale, int bx,
@@ -556,6 +558,8 @@ void stencil_lds_tune(float* next, const float* curr, int gx, int gy, float xcfl
   CME_REQUIRE((int64_t)gx * gy * 4 < (int64_t)0x7FFFFFF0, "stencil_lds_tune: grid too large for 32-bit offsets");
   // nt bit 0: non-temporal streamed loads, bit 1: alternate walk, bit 2: plain (not non-temporal) stores
   const int key = rows * 100 + ahead * 10 + (nt & 1) + (nt & 2 ? 100000 : 0) + (nt & 4 ? 1000000 : 0);
+  // every case is held bitwise to stencil_step(variant 2) by tests/test_gpu_suite_edges.py, which enumerates them
+  // (suite_cases.LDS_TUNE_CASES): a case added here is added to that list
   switch (key) {
     case 1103240: launch_lds_tune<32, 4, 0, true, false>(next, curr, gx, gy, xcfl, ycfl, s); break;
     case 1103260: launch_lds_tune<32, 6, 0, true, false>(next, curr, gx, gy, xcfl, ycfl, s); break;
@@ -630,7 +634,9 @@ void stencil_step2_bc(float* next, const float* curr, int gx, int gy, int order,
     if (wgs(32) < 512) rows = 32;
   }
   if (ahead <= 0) ahead = 2;  // (2 rows of loads ahead: fewer registers, more waves -- faster than 4 at every size)
-  // (rows, ahead): the production choice and the tuning grid of bench/stencil_tune.py --two-step
+  // (rows, ahead): the production choice and the tuning grid of bench/stencil_tune.py --two-step.  Every case is held
+  // bitwise to two stencil_step_bc(variant 2) launches by tests/test_gpu_suite_edges.py, which enumerates them
+  // (suite_cases.LDS2_CASES): a case added here is added to that list
   switch (rows * 10 + ahead) {
     case 644: launch_lds2<64, 4>(next, curr, gx, gy, xcfl, ycfl, scale, s); break;
     case 642: launch_lds2<64, 2>(next, curr, gx, gy, xcfl, ycfl, scale, s); break;

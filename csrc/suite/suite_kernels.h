@@ -43,14 +43,16 @@ void stencil_step(float* next, const float* curr, int gx, int gy, int order, flo
 void stencil_step_bc(float* next, const float* curr, int gx, int gy, int order, float xcfl, float ycfl, int variant,
                      float scale, bool with_bc, hipStream_t s);
 // the LDS variant at order 8 with its knobs exposed (rows per wave 32/64/128, rows loaded ahead 4/8, non-temporal
-// streamed loads), interior only: bench/stencil_tune.py
+// streamed loads), interior only: bench/stencil_tune.py.  Every instantiated case is bitwise stencil_step(variant 2)
+// (tests/test_gpu_suite_edges.py)
 void stencil_lds_tune(float* next, const float* curr, int gx, int gy, float xcfl, float ycfl, int rows, int ahead,
                       int nt, hipStream_t s);
 // next(border) = curr(border) * scale  (border width b)
 void stencil_bc(float* next, const float* curr, int gx, int gy, int b, float scale, hipStream_t s);
 // TWO time steps (each: interior stencil + border * scale) in one sweep of the grid: the LDS walk with temporal
-// blocking (order 8); bitwise two stencil_step_bc launches
-// (rows, ahead <= 0: the production walk -- 64 rows per wave, 4 rows of loads ahead; others: tuning)
+// blocking (order 8); bitwise two stencil_step_bc launches at every instantiated (rows, ahead)
+// (tests/test_suite_gpu.py, tests/test_gpu_suite_edges.py)
+// (rows, ahead <= 0: the production pick -- rows by the grid size, 2 rows of loads ahead; others: tuning)
 void stencil_step2_bc(float* next, const float* curr, int gx, int gy, int order, float xcfl, float ycfl, float scale,
                       hipStream_t s, int rows = 0, int ahead = 0);
 
