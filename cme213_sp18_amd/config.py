@@ -87,6 +87,13 @@ class TrainConfig:
     ema_warmup: bool = False    # --ema-warmup: the decay of update t is min(DECAY, (1 + t) / (10 + t))
     eval_weights: str = ""      # --eval-weights ema | current: the weights --eval-every reads ("": ema when averaging)
     use_ema: bool = False       # --use-ema: the averaged weights become the final ones (outputs and checkpoint)
+    lr_plateau: float | None = None  # --lr-plateau FACTOR: reduce the rate on a validation plateau (optim.Plateau; dp)
+    plateau_patience: int = 10  # --plateau-patience: non-improving evaluations tolerated before a reduction
+    plateau_threshold: float = 1e-4   # --plateau-threshold
+    plateau_threshold_mode: str = "rel"  # --plateau-threshold-mode rel | abs
+    plateau_cooldown: int = 0   # --plateau-cooldown: evaluations not counted after a reduction
+    plateau_min_factor: float = 0.0   # --plateau-min-factor: the scale's lower bound
+    plateau_monitor: str = "loss"     # --plateau-monitor loss | accuracy
 
     @property
     def schedule(self):
@@ -99,6 +106,17 @@ class TrainConfig:
         return Schedule(kind, unit=self.lr_unit, warmup=self.warmup, warmup_start=self.warmup_start,
                         size=self.lr_step_size, gamma=self.lr_gamma, total=self.lr_total,
                         end_factor=self.lr_end_factor, min_factor=self.lr_min_factor)
+
+    @property
+    def plateau(self):
+        """The optim.Plateau of the --lr-plateau / --plateau-* flags, or None."""
+        from .optim import Plateau
+
+        if self.lr_plateau is None:
+            return None
+        return Plateau(float(self.lr_plateau), self.plateau_patience, self.plateau_threshold,
+                       self.plateau_threshold_mode, self.plateau_cooldown, self.plateau_min_factor,
+                       monitor=self.plateau_monitor)
 
     @property
     def ema_rule(self):
@@ -329,6 +347,23 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--use-ema", action="store_true", default=None,
                     help="after training, make the averaged weights the current ones: the precision, the predictions "
                          "and the final checkpoint are those of the average; needs --ema")
+    ap.add_argument("--lr-plateau", type=float, metavar="FACTOR",
+                    help="reduce the learning rate on a validation plateau (torch's ReduceLROnPlateau), decided on the "
+                         "device behind every --eval-every evaluation: after more than --plateau-patience evaluations "
+                         "that do not improve, every later update's rate is multiplied by FACTOR (0 < FACTOR < 1), on "
+                         "top of --lr-schedule; sequential and parallel run alike; `plateau` event in --log-json; data "
+                         "parallel only")
+    ap.add_argument("--plateau-patience", type=int, help="non-improving evaluations tolerated (default 10)")
+    ap.add_argument("--plateau-threshold", type=float,
+                    help="an evaluation improves only when it beats the best by more than this (default 1e-4)")
+    ap.add_argument("--plateau-threshold-mode", choices=["rel", "abs"],
+                    help="the threshold as a fraction of the best (rel, default) or as a difference (abs)")
+    ap.add_argument("--plateau-cooldown", type=int,
+                    help="evaluations after a reduction that are not counted (default 0)")
+    ap.add_argument("--plateau-min-factor", type=float,
+                    help="the lower bound of the accumulated factor, in [0, 1] (default 0)")
+    ap.add_argument("--plateau-monitor", choices=["loss", "accuracy"],
+                    help="the validation metric the rule watches (default loss)")
     ap.add_argument("--gpus", type=int,
                     help="number of ranks, one per GPU (the reference's mpirun -np N); started here when no "
                          "launcher started this process")
@@ -364,7 +399,7 @@ def parse_config(argv=None) -> TrainConfig:
     if cfg.parallel == "tp" and (cfg.lr_schedule or cfg.clip_norm is not None):
         ap.error("--parallel tp applies plain SGD at one rate only; --lr-schedule / --clip-norm need --parallel dp")
     if not cfg.lr_schedule and any(k.startswith("lr_") or k.startswith("warmup") for k in explicit
-                                   if k != "lr_schedule"):
+                                   if k not in ("lr_schedule", "lr_plateau")):
         ap.error("--lr-gamma, --lr-step-size, --lr-total, --lr-end-factor, --lr-min-factor, --lr-unit, --warmup and "
                  "--warmup-start need --lr-schedule")
     # keeping the best weights acts on the device-side evaluations of the data-parallel trainer
@@ -389,6 +424,15 @@ def parse_config(argv=None) -> TrainConfig:
         ap.error(f"{', '.join(ema_flags)} need(s) --ema DECAY")
     if cfg.use_ema and cfg.restore_best:
         ap.error("--use-ema and --restore-best both choose the final weights: give one of them")
+    # the plateau rule acts on the device-side evaluations of the data-parallel trainer
+    plateau_flags = sorted("--" + k.replace("_", "-") for k in explicit if k.startswith("plateau_"))
+    if plateau_flags and cfg.lr_plateau is None:
+        ap.error(f"{', '.join(plateau_flags)} need(s) --lr-plateau FACTOR")
+    if cfg.lr_plateau is not None and cfg.parallel == "tp":
+        ap.error("--lr-plateau acts on the device-side evaluation and the apply launch, which are data-parallel only; "
+                 "it needs --parallel dp")
+    if cfg.lr_plateau is not None and not cfg.eval_every > 0:
+        ap.error("--lr-plateau acts on the evaluations: it needs --eval-every N > 0")
     if cfg.augment_shift is None and not cfg.augment_affine and not cfg.augment_elastic and any(
             k in explicit for k in ("augment_shift_y", "augment_seed", "image_shape")):
         ap.error("--augment-shift-y, --augment-seed and --image-shape need --augment-shift")
@@ -399,6 +443,7 @@ def parse_config(argv=None) -> TrainConfig:
         cfg.optim  # the hyper-parameters' ranges (optim.Optimizer validates)
         cfg.schedule
         cfg.ema_rule  # (optim.Ema validates the decay)
+        cfg.plateau  # (optim.Plateau validates the ranges)
         from .optim import resolve_policy
 
         resolve_policy(None, cfg.clip_norm)

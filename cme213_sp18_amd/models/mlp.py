@@ -99,6 +99,17 @@ def predict(nn: NeuralNetwork, X, shift: bool = True) -> np.ndarray:
     return cpu().predict(*nn.params, _x64(X), shift)
 
 
+def eval_triple(nn: NeuralNetwork, X, labels, shift: bool = True) -> tuple[float, float, float]:
+    """(n, correct, loss_sum) of a labelled set in fp64 on the host -- what a device evaluation leaves in its stats slot
+    (csrc/mlp/eval.h): the count, the count of first-maximum predictions that hit the label and the sum of
+    -log(yhat[label]) without the regulariser."""
+    labels = np.ascontiguousarray(labels, dtype=np.int64)
+    yc = feedforward(nn, X, shift).yc
+    n = labels.shape[0]
+    correct = int((yc.argmax(1) == labels).sum())
+    return float(n), float(correct), float(-np.log(yc[np.arange(n), labels]).sum())
+
+
 def numgrad(nn: NeuralNetwork, X, labels, reg: float, shift: bool = True) -> Grads:
     dW1, db1, dW2, db2 = cpu().numgrad(*nn.params, _x64(X), np.ascontiguousarray(labels, np.int32), float(reg),
                                        shift)
@@ -110,7 +121,7 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
           outdir: str = "Outputs", shift: bool = True, ckpt_precision: int = 12, iter0: int = 0,
           shuffle_seed: int | None = None, optimizer=None, optim_state: dict | None = None, schedule=None,
           clip_norm: float | None = None, update_log: list | None = None, augment=None, ema=None,
-          ema_state: dict | None = None) -> list[float]:
+          ema_state: dict | None = None, lr_scale: float | None = None) -> list[float]:
     """Sequential fp64 minibatch SGD on the CPU -- the oracle (neural_network.cpp:219-279).
 
     ``optimizer``: an ``optim.Optimizer`` (None or ``Optimizer.sgd()``: the reference's plain update).  A stateful
@@ -145,6 +156,11 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
     updates, "avg": fp64 over [W1|b1|W2|b2]}, the average starting as a copy of the parameters -- is updated in place
     and so returned, and a later call continues it; None: a fresh one for this call, dropped afterwards.
 
+    ``lr_scale`` (the parallel trainer's ``plateau=``): the oracle evaluates no validation set, so it takes the scale
+    the plateau rule holds (csrc/mlp/plateau.h) from the caller and stays comparable one epoch at a time: every rate of
+    this call is ``(learning_rate * factor) * lr_scale`` -- the product the apply launch forms, in its order -- and,
+    as under a schedule, plain SGD runs the stateless kSgd rule with its update count in ``optim_state``.
+
     ``grad_check`` runs a numerical gradient check on the first batch (the
     reference's threshold of 1000 made it a no-op; we assert a real bound).
     """
@@ -164,7 +180,7 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
 
     opt = resolve(optimizer)
     schedule, clip = resolve_policy(schedule, clip_norm)
-    policy = schedule is not None or clip > 0.0
+    policy = schedule is not None or clip > 0.0 or lr_scale is not None
     kw = {}
     n, nb = X.shape[0], (X.shape[0] + int(batch_size) - 1) // int(batch_size)
     rates = None
@@ -184,6 +200,11 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
             kw["update_log"] = update_log
         if schedule is not None:  # lr * factor: the fp64 product the apply launch forms
             rates = float(learning_rate) * schedule.factors(int(st["t"]), int(epochs) * nb, nb)
+        if lr_scale is not None:  # (lr * f) * scale: csrc/mlp/plateau.h plateau_rate
+            if not float(lr_scale) >= 0.0:
+                raise ValueError(f"lr_scale must be >= 0, got {lr_scale}")
+            base = rates if rates is not None else np.full(int(epochs) * nb, float(learning_rate), np.float64)
+            rates = np.array([cpu().plateau_rate(float(r), float(lr_scale)) for r in base], np.float64)
     elif update_log is not None:
         raise ValueError("update_log needs a schedule, clip_norm or a stateful optimizer")
     from ..optim import new_ema_state, resolve_ema

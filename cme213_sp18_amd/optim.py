@@ -256,6 +256,94 @@ class Ema:
         return cls(float(d["decay"]), bool(d.get("warmup", False))) if d else None
 
 
+PLATEAU_MONITORS = ("loss", "accuracy")  # csrc/mlp/best.h BestMonitor: mode min / mode max
+PLATEAU_THRESHOLD_MODES = ("rel", "abs")  # csrc/mlp/plateau.h PlateauThresholdMode
+PLATEAU_FIELDS = ("evals", "best", "bad", "cooldown_left", "scale", "reductions", "last_metric",
+                  "last_reduced_index")  # the record's 8 doubles, in order
+
+
+@dataclasses.dataclass(frozen=True)
+class Plateau:
+    """Reduce the learning rate when the validation metric stops improving (csrc/mlp/plateau.h):
+    torch.optim.lr_scheduler.ReduceLROnPlateau, decided on the device behind every evaluation.  The rule keeps a
+    ``scale`` (1.0 at the start) that multiplies every update's rate after the schedule's factor: ``(lr * f) * scale``.
+    After more than ``patience`` evaluations that are not better than the best by ``threshold`` (``rel``: a fraction of
+    the best; ``abs``: a difference) the scale becomes ``max(scale * factor, min_factor)`` -- unless that changes it by
+    no more than ``eps`` -- and the next ``cooldown`` evaluations are not counted.  ``monitor``: the validation
+    ``loss`` (lower is better) or ``accuracy`` (higher is better)."""
+    factor: float = 0.1
+    patience: int = 10
+    threshold: float = 1e-4
+    threshold_mode: str = "rel"
+    cooldown: int = 0
+    min_factor: float = 0.0
+    eps: float = 1e-8
+    monitor: str = "loss"
+
+    def __post_init__(self):
+        if not 0.0 < float(self.factor) < 1.0:
+            raise ValueError(f"factor must be in (0, 1), got {self.factor}")
+        for name in ("patience", "cooldown"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or int(v) != v or int(v) < 0 or int(v) >= 2 ** 31:
+                raise ValueError(f"{name} must be an integer >= 0, got {v!r}")
+        if not (float(self.threshold) >= 0.0 and math.isfinite(float(self.threshold))):
+            raise ValueError(f"threshold must be >= 0, got {self.threshold}")
+        if self.threshold_mode not in PLATEAU_THRESHOLD_MODES:
+            raise ValueError(f"threshold_mode must be one of {PLATEAU_THRESHOLD_MODES}, got {self.threshold_mode!r}")
+        if not 0.0 <= float(self.min_factor) <= 1.0:
+            raise ValueError(f"min_factor must be in [0, 1], got {self.min_factor}")
+        if not (float(self.eps) >= 0.0 and math.isfinite(float(self.eps))):
+            raise ValueError(f"eps must be >= 0, got {self.eps}")
+        if self.monitor not in PLATEAU_MONITORS:
+            raise ValueError(f"monitor must be one of {PLATEAU_MONITORS}, got {self.monitor!r}")
+
+    @property
+    def monitor_code(self) -> int:
+        return PLATEAU_MONITORS.index(self.monitor)
+
+    def native(self) -> tuple:
+        """(monitor, factor, patience, threshold, threshold_mode, cooldown, min_factor, eps): the native calls' rule."""
+        return (self.monitor_code, float(self.factor), int(self.patience), float(self.threshold),
+                PLATEAU_THRESHOLD_MODES.index(self.threshold_mode), int(self.cooldown), float(self.min_factor),
+                float(self.eps))
+
+    def key(self) -> tuple:
+        return ("plateau",) + self.native()
+
+    def as_meta(self) -> dict:
+        return {"factor": float(self.factor), "patience": int(self.patience), "threshold": float(self.threshold),
+                "threshold_mode": self.threshold_mode, "cooldown": int(self.cooldown),
+                "min_factor": float(self.min_factor), "eps": float(self.eps), "monitor": self.monitor}
+
+    @classmethod
+    def from_meta(cls, d: dict | None) -> "Plateau | None":
+        return cls(**d) if d else None
+
+
+def resolve_plateau(plateau) -> Plateau | None:
+    if plateau is not None and not isinstance(plateau, Plateau):
+        raise TypeError("plateau must be a Plateau or None")
+    return plateau
+
+
+def plateau_record_dict(rec) -> dict:
+    """The record's 8 doubles as a dict: counts as ints, ``best`` / ``scale`` / ``last_metric`` as floats."""
+    r = [float(v) for v in np.asarray(rec, np.float64).reshape(-1)]
+    ints = ("evals", "bad", "cooldown_left", "reductions", "last_reduced_index")
+    return {k: (int(v) if k in ints else v) for k, v in zip(PLATEAU_FIELDS, r)}
+
+
+def plateau_record_array(d) -> np.ndarray:
+    """The inverse of ``plateau_record_dict`` (a dict, or 8 numbers) as a float64 array."""
+    if isinstance(d, dict):
+        return np.array([float(d[k]) for k in PLATEAU_FIELDS], np.float64)
+    a = np.array(d, np.float64).reshape(-1)
+    if a.size != len(PLATEAU_FIELDS):
+        raise ValueError("a plateau record holds 8 numbers")
+    return a
+
+
 def resolve_ema(ema) -> Ema | None:
     if ema is not None and not isinstance(ema, Ema):
         raise TypeError("ema must be an Ema or None")

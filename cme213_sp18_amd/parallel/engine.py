@@ -193,6 +193,10 @@ class MlpEngine:
         # keeping the best validation weights (enable_keep_best): None = nothing allocated, nothing launched; else the
         # rule, the best arena, the per-workgroup records (csrc/mlp/best.h) and, for data parallel, the [R][3] rows
         self._best = None
+        # reducing the rate on a validation plateau (set_plateau): None = nothing allocated, nothing launched; else the
+        # rule (optim.Plateau), the ONE record of 8 doubles (csrc/mlp/plateau.h) whose scale word the apply launch reads
+        # and, for data parallel, the [R][3] rows of a decision
+        self._plateau = None
         # an exponential moving average of the parameters (set_ema): None = nothing allocated, nothing launched; else
         # the rule, the averaged arena, the per-workgroup records (csrc/mlp/ema.h) and, once an evaluation has read the
         # average, its own derived copies of W1 and (split paths) the MlpStep bound to them
@@ -888,12 +892,12 @@ class MlpEngine:
 
     @property
     def policy_set(self) -> bool:
-        return self.schedule is not None or self.clip_norm > 0.0
+        return self.schedule is not None or self.clip_norm > 0.0 or self._plateau is not None
 
     @property
     def uses_apply_launch(self) -> bool:
-        """apply() is the one launch of csrc/mlp/optim.hip (a stateful rule, or plain SGD under a schedule or
-        clipping) rather than sgd(lr)."""
+        """apply() is the one launch of csrc/mlp/optim.hip (a stateful rule, or plain SGD under a schedule, clipping
+        or a plateau rule) rather than sgd(lr)."""
         return self.optimizer is not None or self.policy_set
 
     def set_update_policy(self, schedule=None, clip_norm=None) -> None:
@@ -1085,7 +1089,7 @@ class MlpEngine:
                           int(self.opt_rec.shape[0]), win.data_ptr() if win is not None else 0,
                           int(win.numel()) - 2 if win is not None else 0,
                           self.clip_partials.data_ptr() if npart else 0, npart, self.clip_norm,
-                          self.opt_last.data_ptr(), st)
+                          self.opt_last.data_ptr(), st, self._plateau_word())
             return
         with torch.no_grad():
             if float(self.grads[self.status_index]) != 0.0:
@@ -1098,6 +1102,8 @@ class MlpEngine:
             lr_t = float(lr)
             if self._win_host is not None:
                 lr_t = float(cpu().window_rate(float(lr), float(self._win_host[0]), self._win_host[1], t))
+            if self._plateau is not None:  # (lr * f) * scale, as the apply launch forms it
+                lr_t = float(cpu().plateau_rate(lr_t, float(self._plateau["rec"][cpu().plateau_scale_word])))
             norm, coef = float("nan"), 1.0
             if self.clip_norm > 0.0:
                 norm, coef = cpu().grad_clip(g, self.clip_segments(), self.clip_norm)
@@ -1402,11 +1408,18 @@ class MlpEngine:
         """This rank's {n, correct, loss_sum} of stats slot ``slot`` into row ``rank`` of best_rows, zero into every
         other row: a SUM all-reduce of the buffer is then an exact all-gather.  On the current stream; no host read on
         the hip backend."""
-        b = self._best_set()
-        ev = self._eval_set(slot)
-        rows = b["rows"]
+        rows = self._best_set()["rows"]
         if rows is None:
             raise RuntimeError("enable_keep_best(ranks=R) with R > 1 first")
+        self.pack_rows(slot, rank, rows)
+
+    def pack_rows(self, slot: int, rank: int, rows) -> None:
+        """pack_best_rows into any [R][3] float64 buffer on the engine's device (the plateau rule's, when keep-best is
+        off)."""
+        ev = self._eval_set(slot)
+        if rows is None or rows.dtype != torch.float64 or rows.ndim != 2 or rows.shape[1] != 3 \
+                or not rows.is_contiguous():
+            raise ValueError("rows must be a contiguous [R][3] float64 tensor")
         if not 0 <= int(rank) < rows.shape[0]:
             raise IndexError(f"rank {rank} outside [0, {rows.shape[0]})")
         if self.backend == "hip":
@@ -1507,6 +1520,105 @@ class MlpEngine:
                     dst.copy_(src.reshape(dst.shape).to(dst.dtype))
             b["rec"].copy_(torch.from_numpy(rec).expand_as(b["rec"]))
         b["fresh"] = False
+
+    # ------------------------------------------------------- reduce the rate on a plateau
+    def set_plateau(self, rule, ranks: int = 1) -> None:
+        """Reduce the learning rate when the validation metric stops improving (optim.Plateau; csrc/mlp/plateau.h).
+        None: nothing allocated, nothing launched, apply() as it stands.  A rule allocates the one record of 8 doubles
+        (reset to the start state) and, for ``ranks`` > 1, the [ranks][3] rows of a data-parallel decision; from then
+        on every update -- plain SGD's too, as the stateless kSgd rule -- goes through the apply launch, which
+        multiplies its rate by the record's scale word: ``(lr * f) * scale``.  enqueue_plateau() behind an evaluation
+        advances the record.  Setting the rule it already has keeps the record."""
+        from ..optim import resolve_plateau
+
+        rule = resolve_plateau(rule)
+        ranks = int(ranks)
+        if ranks < 1:
+            raise ValueError("ranks must be >= 1")
+        p = self._plateau
+        if rule is not None and p is not None and p["rule"] == rule and p["ranks"] == ranks:
+            return
+        had, had_policy = self.uses_apply_launch, self.policy_set
+        dev = self.device
+        if rule is None:
+            self._plateau = None
+            if had_policy and not self.policy_set:
+                self.opt_last = None
+                if self.optimizer is None:
+                    self._alloc_update_state()
+            return
+        self._plateau = dict(rule=rule, ranks=ranks, rec=torch.zeros(8, dtype=torch.float64, device=dev),
+                             rows=torch.zeros(ranks, 3, dtype=torch.float64, device=dev) if ranks > 1 else None)
+        if not had:
+            self._alloc_update_state()
+        if not had_policy:
+            self.opt_last = torch.tensor([-1.0, float("nan"), float("nan"), 1.0], dtype=torch.float64, device=dev)
+        self.reset_plateau()
+
+    def _plateau_set(self) -> dict:
+        if self._plateau is None:
+            raise RuntimeError("set_plateau() first")
+        return self._plateau
+
+    def _plateau_word(self) -> int:
+        """The address of the record's scale word for the apply launch (0 without a rule)."""
+        p = self._plateau
+        return 0 if p is None else p["rec"].data_ptr() + 8 * int(hip().plateau_scale_word)
+
+    @property
+    def plateau_rows(self):
+        """The [ranks][3] device buffer of a data-parallel decision (None for one rank)."""
+        return self._plateau_set()["rows"]
+
+    def reset_plateau(self) -> None:
+        """The record back to its start state {0, +inf | -inf, 0, 0, 1.0, 0, NaN, -1}: the scale is 1 again."""
+        p = self._plateau_set()
+        with torch.no_grad():
+            p["rec"].copy_(torch.from_numpy(cpu().plateau_start(p["rule"].monitor_code)))
+
+    def enqueue_plateau(self, slot: int, rows=None) -> None:
+        """One decision on the current stream, behind enqueue_eval(slot): from stats slot ``slot`` (one process) or from
+        ``rows`` (a contiguous [R][3] float64 tensor of {n, correct, loss_sum} per rank, summed in rank order; on the
+        hip backend a device tensor that stays alive until the launch has run).  One workgroup advances the record; the
+        updates enqueued behind it use the new scale.  No host read, no sync, no allocation on the hip backend: legal
+        under stream capture."""
+        p = self._plateau_set()
+        ev = self._eval_set(slot)
+        if rows is not None and (rows.dtype != torch.float64 or rows.ndim != 2 or rows.shape[1] != 3
+                                 or rows.shape[0] < 1 or not rows.is_contiguous()):
+            raise ValueError("rows must be a contiguous [R][3] float64 tensor, R >= 1")
+        if self.backend == "hip":
+            if rows is not None and rows.device != self.device:
+                raise ValueError("rows must live on the engine's device")
+            hip().mlp_plateau(*p["rule"].native(), p["rec"].data_ptr(),
+                              0 if rows is not None else ev["stats"].data_ptr() + int(slot) * ev["stats"].shape[1] * 8,
+                              rows.data_ptr() if rows is not None else 0,
+                              int(rows.shape[0]) if rows is not None else 1,
+                              torch.cuda.current_stream(self.device).cuda_stream)
+            return
+        with torch.no_grad():
+            triples = rows.cpu().numpy() if rows is not None else self._slot_triple(ev, slot)
+            rec, _ = cpu().plateau_decide(p["rec"].cpu().numpy(), p["rule"].native(), triples)
+            p["rec"].copy_(torch.from_numpy(rec))
+
+    def plateau_record(self) -> np.ndarray:
+        """The record as raw doubles [8].  Synchronises."""
+        return self._plateau_set()["rec"].cpu().numpy().copy()
+
+    def plateau_state(self) -> dict:
+        """The record as a dict: evals, best, bad, cooldown_left, scale, reductions, last_metric, last_reduced_index.
+        The one sync: a 64-byte read."""
+        from ..optim import plateau_record_dict
+
+        return plateau_record_dict(self.plateau_record())
+
+    def set_plateau_state(self, record) -> None:
+        """Resume: ``record`` = the 8 doubles of a record, or a plateau_state() dict."""
+        from ..optim import plateau_record_array
+
+        p = self._plateau_set()
+        with torch.no_grad():
+            p["rec"].copy_(torch.from_numpy(plateau_record_array(record)))
 
     # ------------------------------------------------------- an average of the weights
     @property

@@ -47,7 +47,7 @@ class TensorParallelTrainer:
     def __init__(self, nn, comm: Communicator | None = None, device=None, dtype: str = "f32",
                  batch_size: int = 800, backend: str = "hip", shift: bool = True, normalize: bool = False,
                  path: str = "auto", allreduce: str = "auto", shuffle_seed: int | None = None, optimizer=None,
-                 schedule=None, clip_norm=None, augment=None, ema=None):
+                 schedule=None, clip_norm=None, augment=None, ema=None, plateau=None):
         from ..optim import resolve
 
         # the shard's update stays inside its weight-gradient launch (plain SGD); the stateful rules are
@@ -58,6 +58,9 @@ class TensorParallelTrainer:
         if schedule is not None or clip_norm is not None:
             raise ValueError("tensor parallelism applies plain SGD at one rate only: a learning-rate schedule or "
                              "gradient-norm clipping needs data parallelism (--parallel dp)")
+        if plateau is not None:
+            raise ValueError("tensor parallelism has no device-side evaluation and applies plain SGD at one rate only: "
+                             "reducing the rate on a validation plateau needs data parallelism (--parallel dp)")
         if ema is not None:
             raise ValueError("tensor parallelism keeps no average of the weights: every rank holds a shard, and the "
                              "averaging launch runs over the whole arena; weight averaging (ema) needs data "

@@ -231,6 +231,9 @@ class TrainStats:
     best: dict | None = None
     stopped: bool = False
     stop_index: int = -1
+    # DataParallelTrainer(plateau=...): the rule's record after this call (engine.plateau_state(): evals, best, bad,
+    # cooldown_left, scale, reductions, last_metric, last_reduced_index); None without a rule
+    plateau: dict | None = None
 
     @property
     def images_per_sec(self) -> float:
@@ -243,7 +246,8 @@ class DataParallelTrainer:
                  normalize: bool = False, path: str = "auto", allreduce: str = "auto", overlap: bool = True,
                  overlap_chunks: int = 0, fuse_allreduce: bool = True, executor: str = "auto",
                  grad_wire: str = "auto", fused_form: str = "auto", shuffle_seed: int | None = None,
-                 optimizer=None, schedule=None, clip_norm=None, augment=None, ema=None):
+                 optimizer=None, schedule=None, clip_norm=None, augment=None, ema=None,
+                 plateau=None):
         self.nn = nn
         # an exponential moving average of the parameters (optim.Ema; None: nothing allocated, nothing launched): one
         # more launch behind every applied update folds the parameters into a resident averaged arena, on every sync
@@ -267,7 +271,14 @@ class DataParallelTrainer:
 
         self.schedule, clip = resolve_policy(schedule, clip_norm)
         self.clip_norm = clip if clip > 0.0 else None
-        self._policy = self.schedule is not None or self.clip_norm is not None
+        # reduce the rate on a validation plateau (optim.Plateau; None: nothing allocated, nothing launched): behind
+        # every evaluation of train() one more launch decides on the device (csrc/mlp/plateau.h) and the apply launch
+        # multiplies every update's rate by the record's scale -- so, like a schedule, it sends every update through
+        # gradient mode + the apply launch
+        from ..optim import resolve_plateau
+
+        self.plateau = resolve_plateau(plateau)
+        self._policy = self.schedule is not None or self.clip_norm is not None or self.plateau is not None
         self._apply_launch = self.optimizer is not None or self._policy
         self._win_left = 0  # updates the schedule window still covers on the hand-driven step() path
         self.native_reason = ""  # why native_plan() last returned None for a reason of the optimizer's
@@ -318,6 +329,7 @@ class DataParallelTrainer:
         self.engine.set_params(*nn.params)
         self.engine.set_optimizer(self.optimizer)
         self.engine.set_update_policy(self.schedule, self.clip_norm)
+        self.engine.set_plateau(self.plateau, ranks=self.R)
         self.engine.set_ema(self.ema)
         # training reads nothing of a1 after a step: the wide fused forward + head launch skips its 13 MB store
         # at H = 4096 (bench/wide_ag_ab.py: -1.4 us/step fp32, -2.1 us bf16)
@@ -503,6 +515,8 @@ class DataParallelTrainer:
         if e._ema is not None:  # ... and the same averaged weights and count
             w = torch.cat([w, as_words(e._ema["arena"].detach().reshape(-1)).to(torch.int64),
                            e._ema["rec"][0].view(torch.int64)])
+        if e._plateau is not None:  # ... and the same plateau record: the same scale on every rank
+            w = torch.cat([w, e._plateau["rec"].view(torch.int64)])
         idx = torch.arange(1, w.numel() + 1, device=w.device, dtype=torch.int64)
         # two position-weighted sums, folded below 2^52 so they travel exactly as float64
         h = [int(w.sum().item()) % (1 << 52), int(((w % 65521) * (idx % 65519)).sum().item()) % (1 << 52)]
@@ -838,6 +852,8 @@ class DataParallelTrainer:
                       "iters": len(self._best_iters)},)
         if e._ema is not None:  # the averaged arena and every workgroup's record, tagged by name
             snap += ({"kind": "ema", "arena": e._ema["arena"].clone(), "rec": e._ema["rec"].clone()},)
+        if e._plateau is not None:  # the plateau record: a recovered epoch repeats its rates
+            snap += ({"kind": "plateau", "rec": e._plateau["rec"].clone()},)
         return snap
 
     def _restore(self, snap):
@@ -849,6 +865,8 @@ class DataParallelTrainer:
         if "ema" in tagged and e._ema is not None:
             e._ema["arena"].copy_(tagged["ema"]["arena"])
             e._ema["rec"].copy_(tagged["ema"]["rec"])
+        if "plateau" in tagged and e._plateau is not None:
+            e._plateau["rec"].copy_(tagged["plateau"]["rec"])
         e.params.copy_(snap[0])
         if snap[1] is not None:
             e.W1g.copy_(snap[1])
@@ -870,7 +888,8 @@ class DataParallelTrainer:
             (self.optimizer.key(),) if self.optimizer is not None else ()) + (
             (("schedule",) + self.schedule.key(),) if self.schedule is not None else ()) + (
             (("clip", float(self.clip_norm)),) if self.clip_norm is not None else ()) + (
-            (self.ema.key(),) if self.ema is not None else ())
+            (self.ema.key(),) if self.ema is not None else ()) + (
+            (self.plateau.key(),) if self.plateau is not None else ())
         g = self._graphs.get(key)
         if g is not None:
             return g
@@ -910,7 +929,9 @@ class DataParallelTrainer:
             return None
         if self._policy:
             what = " and ".join(w for w, on in (("a learning-rate schedule", self.schedule is not None),
-                                                ("gradient-norm clipping", self.clip_norm is not None)) if on)
+                                                ("gradient-norm clipping", self.clip_norm is not None),
+                                                ("a plateau rule (reduce the rate on a validation plateau)",
+                                                 self.plateau is not None)) if on)
             self.native_reason = (f"{what}: every step runs in gradient mode followed by the apply launch, which "
                                   "reads the update's rate and the gradient norm on the device")
             if e.backend == "hip":
@@ -1123,6 +1144,11 @@ class DataParallelTrainer:
             raise ValueError("patience, min_delta and stop_check_every need keep_best='loss' or 'accuracy'")
         if keep_best is not None and not int(eval_every) > 0:
             raise ValueError("train(keep_best=...) needs eval_every > 0: the rule acts on the evaluations")
+        if self.plateau is not None and not int(eval_every) > 0:
+            raise ValueError("a trainer with plateau=Plateau(...) needs train(eval_every > 0): the rule acts on the "
+                             "evaluations")
+        if self.plateau is not None and self.engine.eval_slots == 0:
+            raise RuntimeError("a trainer with plateau=Plateau(...) needs a validation set: load_eval() first")
         if eval_weights is None:
             eval_weights = "ema" if self.ema is not None else "current"
         if eval_weights not in ("ema", "current"):
@@ -1172,7 +1198,8 @@ class DataParallelTrainer:
             if on_event is not None:
                 on_event({"event": "eval", "epoch": epoch, "iter": self.iter, "n": r["n"], "loss": r["loss"],
                           "accuracy": r["accuracy"],
-                          **({"weights": eval_weights} if self.ema is not None else {})})
+                          **({"weights": eval_weights} if self.ema is not None else {}),
+                          **({"lr_scale": self.engine.plateau_state()["scale"]} if self.plateau is not None else {})})
 
         def best_enqueued(epoch: int) -> None:
             """The decision behind this epoch's evaluation is on the stream: remember when it was taken and, where the
@@ -1211,8 +1238,7 @@ class DataParallelTrainer:
                 slot = eval_slot(epoch)
                 if slot >= 0:  # behind the epoch's plan, ahead of the epoch's sync (if any)
                     self.engine.enqueue_eval(slot, weights=eval_weights)
-                    if keep_best is not None:
-                        self._enqueue_keep_best(slot, eval_weights)
+                    self._enqueue_decisions(slot, keep_best is not None, eval_weights)
                 if xgmi_live or ag_live:
                     self.assert_comm_ok()  # syncs; every rank raises together
                 self.iter += len(plan.steps)
@@ -1260,8 +1286,7 @@ class DataParallelTrainer:
             slot = eval_slot(epoch)
             if slot >= 0:
                 self.engine.enqueue_eval(slot, weights=eval_weights)
-                if keep_best is not None:
-                    self._enqueue_keep_best(slot, eval_weights)
+                self._enqueue_decisions(slot, keep_best is not None, eval_weights)
             if xgmi_live or ag_live:
                 self.assert_comm_ok()
             if slot >= 0:
@@ -1311,6 +1336,8 @@ class DataParallelTrainer:
                     stats.best = {"index": i, "iter": self._best_iters[i] if i < len(self._best_iters) else None,
                                   "epoch": ep, "metric": st["best_metric"], "monitor": st["monitor"],
                                   "loss": ev["loss"] if ev else None, "accuracy": ev["accuracy"] if ev else None}
+            if self.plateau is not None:
+                stats.plateau = self.engine.plateau_state()
             self.comm.barrier()
         finally:
             self._win_left = 0  # (a hand-driven step() after this call refills the window from the device's count)
@@ -1321,6 +1348,22 @@ class DataParallelTrainer:
         return stats
 
     # ------------------------------------------------------- keep the best weights
+    def _enqueue_decisions(self, slot: int, keep_best: bool, weights: str = "current") -> None:
+        """The launches behind enqueue_eval(slot): keep-best's and / or the plateau rule's.  Both decide from the same
+        evaluation -- whatever weights it read -- and, at R > 1, from the same gathered rows: one pack and one
+        all-reduce per evaluation feed both."""
+        if keep_best:
+            self._enqueue_keep_best(slot, weights)
+        if self.plateau is None:
+            return
+        e = self.engine
+        if self.R == 1:
+            e.enqueue_plateau(slot)
+        elif keep_best:  # (launches on one stream are ordered: the rows keep-best gathered are still in place)
+            e.enqueue_plateau(slot, e.best_rows)
+        else:
+            e.enqueue_plateau(slot, self._gather_rows(slot, e.plateau_rows))
+
     def _enqueue_keep_best(self, slot: int, weights: str = "current") -> None:
         """The decision behind enqueue_eval(slot).  One rank: the launch reads the stats slot itself.  R > 1: pack this
         rank's triple into its row, SUM all-reduce the [R][3] rows (an exact all-gather: every other rank wrote zeros),
@@ -1329,10 +1372,14 @@ class DataParallelTrainer:
         if self.R == 1:
             e.enqueue_keep_best(slot, weights=weights)
             return
+        e.enqueue_keep_best(slot, self._gather_rows(slot, e.best_rows), weights=weights)
+
+    def _gather_rows(self, slot: int, rows):
+        """Every rank's {n, correct, loss_sum} of stats slot ``slot`` in ``rows`` ([R][3] doubles), on every rank."""
         from .comm import TorchDistComm
 
-        e.pack_best_rows(slot, self.rank)
-        rows = e.best_rows
+        e = self.engine
+        e.pack_rows(slot, self.rank, rows)
         if self.allreduce_mode == "host":
             import torch.distributed as dist
 
@@ -1345,7 +1392,19 @@ class DataParallelTrainer:
             rows.copy_(g)
         else:
             self.comm.allreduce_(rows)
-        e.enqueue_keep_best(slot, rows, weights=weights)
+        return rows
+
+    # ------------------------------------------------------- reduce the rate on a plateau
+    def plateau_state(self) -> dict:
+        """The plateau rule's record (engine.plateau_state()).  Synchronises."""
+        return self.engine.plateau_state()
+
+    def set_plateau_state(self, record) -> None:
+        """Resume: the record of a checkpoint."""
+        self.engine.set_plateau_state(record)
+
+    def reset_plateau(self) -> None:
+        self.engine.reset_plateau()
 
     def enable_keep_best(self, monitor: str = "loss", min_delta: float = 0.0, patience: int | None = None) -> None:
         """What train(keep_best=...) does on entry; needed by hand only ahead of set_best_state() on a resume."""

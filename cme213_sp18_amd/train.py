@@ -92,7 +92,8 @@ def run(cfg: TrainConfig) -> dict:
         jlog({"event": "config", "world": world, "device": str(device), **placement, **{
             k: v for k, v in vars(cfg).items() if isinstance(v, (int, float, str, bool))},
             "augment": aug_meta,
-            "ema": cfg.ema_rule.as_meta() if cfg.ema_rule is not None else None})
+            "ema": cfg.ema_rule.as_meta() if cfg.ema_rule is not None else None,
+            "plateau": cfg.plateau.as_meta() if cfg.plateau is not None else None})
         log0(rank, f"Number of processes = {world}")
         log0(rank, f"Device = {device} ({torch.cuda.get_device_name(device) if device.type == 'cuda' else 'cpu'})")
         if cfg.grade == 4:
@@ -112,7 +113,10 @@ def run(cfg: TrainConfig) -> dict:
         meta = {}
         opt = cfg.optim
         sched, clip = cfg.schedule, cfg.clip_norm
-        policy = sched is not None or clip is not None  # (plain SGD then keeps an update count too: optim_t)
+        plateau = cfg.plateau  # an optim.Plateau or None
+        plateau_saved = None  # the checkpoint's plateau record (continued when the flags agree)
+        # (plain SGD then keeps an update count too: optim_t)
+        policy = sched is not None or clip is not None or plateau is not None
         keeps_state = opt.stateful or policy
         opt_state = None  # the checkpoint's optimizer state (both runs continue it)
         best_rule = ({"monitor": cfg.keep_best, "min_delta": float(cfg.min_delta), "patience": cfg.patience}
@@ -155,6 +159,17 @@ def run(cfg: TrainConfig) -> dict:
                            "checkpoint's" + (" (it starts from the resumed weights)" if ema is not None else ""))
             elif saved_ema is not None:
                 ema_saved = saved_ema
+            from .optim import Plateau
+
+            saved_plateau = meta.get("plateau")
+            saved_plateau_rule = Plateau.from_meta(saved_plateau["rule"]) if saved_plateau else None
+            if saved_plateau_rule != plateau:
+                log0(rank, f"warning: the checkpoint was trained with the plateau rule "
+                           f"{saved_plateau['rule'] if saved_plateau else None}, this run uses "
+                           f"{plateau.as_meta() if plateau is not None else None}: the rate's scale does not continue "
+                           "the checkpoint's" + (" (it starts at 1)" if plateau is not None else ""))
+            elif saved_plateau:
+                plateau_saved = saved_plateau["record"]
             if meta.get("shuffle_seed") != cfg.shuffle_seed:
                 log0(rank, f"warning: the checkpoint was trained with --shuffle-seed {meta.get('shuffle_seed')}, this "
                            f"run uses {cfg.shuffle_seed}: the epochs' orders do not continue the checkpoint's")
@@ -186,11 +201,37 @@ def run(cfg: TrainConfig) -> dict:
                     W1a, b1a, W2a, b2a = ema_saved["params"]
                     seq_ema = {"t": ema_saved["t"], "avg": np.concatenate(
                         [np.asarray(a, np.float64).reshape(-1) for a in (W1a, b1a, W2a, b2a)])}
-            mlp.train(seq_nn, xs, ds.y_train, cfg.learning_rate, cfg.reg, cfg.num_epochs, cfg.batch_size,
-                      False, cfg.print_every, cfg.debug, cfg.outdir, cfg.softmax_shift, cfg.ckpt_precision,
-                      iter0=int(meta.get("iter", 0)), shuffle_seed=cfg.shuffle_seed, optimizer=opt,
-                      optim_state=copy.deepcopy(opt_state), schedule=sched, clip_norm=clip, augment=aug, ema=ema,
-                      ema_state=seq_ema)
+            seq_kw = dict(shuffle_seed=cfg.shuffle_seed, optimizer=opt, schedule=sched, clip_norm=clip, augment=aug,
+                          ema=ema, ema_state=seq_ema)
+            if plateau is None:
+                mlp.train(seq_nn, xs, ds.y_train, cfg.learning_rate, cfg.reg, cfg.num_epochs, cfg.batch_size,
+                          False, cfg.print_every, cfg.debug, cfg.outdir, cfg.softmax_shift, cfg.ckpt_precision,
+                          iter0=int(meta.get("iter", 0)), optim_state=copy.deepcopy(opt_state), **seq_kw)
+            else:
+                # the oracle evaluates no validation set: it runs --eval-every epochs at a time at the scale the rule
+                # holds, the dev split is evaluated on the host in fp64 and the rule (csrc/mlp/plateau.h) decides
+                from ._native import cpu
+                from .optim import new_state, plateau_record_array, plateau_record_dict
+
+                seq_state = copy.deepcopy(opt_state) if opt_state is not None else new_state(
+                    opt, seq_nn.num_params(), policy=True)
+                seq_rec = (plateau_record_array(plateau_saved) if plateau_saved is not None
+                           else cpu().plateau_start(plateau.monitor_code))
+                nb = (xs.shape[0] + cfg.batch_size - 1) // cfg.batch_size
+                it, left = int(meta.get("iter", 0)), cfg.num_epochs
+                while left > 0:
+                    k = min(cfg.eval_every, left)
+                    mlp.train(seq_nn, xs, ds.y_train, cfg.learning_rate, cfg.reg, k, cfg.batch_size, False,
+                              cfg.print_every, cfg.debug, cfg.outdir, cfg.softmax_shift, cfg.ckpt_precision, iter0=it,
+                              optim_state=seq_state, lr_scale=float(seq_rec[cpu().plateau_scale_word]), **seq_kw)
+                    it, left = it + k * nb, left - k
+                    if k == cfg.eval_every:
+                        triple = mlp.eval_triple(seq_nn, xd, ds.y_dev, cfg.softmax_shift)
+                        seq_rec, _ = cpu().plateau_decide(seq_rec, plateau.native(), np.asarray([triple], np.float64))
+                seq_ps = plateau_record_dict(seq_rec)
+                out.update(seq_lr_scale=seq_ps["scale"], seq_lr_reductions=seq_ps["reductions"])
+                log0(rank, f"Sequential plateau rule: scale {seq_ps['scale']:.10g} after {seq_ps['reductions']} "
+                           "reduction(s)")
             out["seq_seconds"] = time.perf_counter() - t
             log0(rank, f"Time for Sequential Training: {out['seq_seconds']:.6f} seconds")
             if cfg.use_ema:  # the sequential run's final weights are its average too
@@ -212,16 +253,19 @@ def run(cfg: TrainConfig) -> dict:
                                        backend=backend, shift=cfg.softmax_shift, normalize=cfg.normalize,
                                        path=cfg.path,
                                        allreduce=tp_allreduce_mode(cfg.allreduce), shuffle_seed=cfg.shuffle_seed,
-                                       optimizer=opt, schedule=sched, clip_norm=clip, augment=aug, ema=ema)
+                                       optimizer=opt, schedule=sched, clip_norm=clip, augment=aug, ema=ema,
+                                       plateau=plateau)
             tr.use_graphs = cfg.use_graphs
         else:
             tr = DataParallelTrainer(nn, comm=comm, device=device, dtype=cfg.dtype, batch_size=cfg.batch_size,
                                      backend=backend, shift=cfg.softmax_shift, use_graphs=cfg.use_graphs,
                                      normalize=cfg.normalize, path=cfg.path, allreduce=cfg.allreduce,
                                      overlap_chunks=cfg.overlap_chunks, shuffle_seed=cfg.shuffle_seed, optimizer=opt,
-                                     schedule=sched, clip_norm=clip, augment=aug, ema=ema)
+                                     schedule=sched, clip_norm=clip, augment=aug, ema=ema, plateau=plateau)
             if opt_state is not None:
                 tr.engine.set_optim_state(opt_state)
+            if plateau_saved is not None:
+                tr.set_plateau_state(plateau_saved)
             if ema_saved is not None:
                 tr.set_ema_state(ema_saved["t"], ema_saved["params"])
         tr.load(ds.x_train, ds.y_train)
@@ -251,7 +295,10 @@ def run(cfg: TrainConfig) -> dict:
                                   "augment": aug_meta,
                                   **({"optimizer": opt.as_meta()} if opt.stateful else {}),
                                   **({"schedule": sched.as_meta()} if sched is not None else {}),
-                                  **({"clip_norm": clip} if clip is not None else {})}
+                                  **({"clip_norm": clip} if clip is not None else {}),
+                                  **({"plateau": {"rule": plateau.as_meta(),
+                                                  "record": tr.engine.plateau_record().tolist()}}
+                                     if plateau is not None else {})}
 
         def ckpt_ema():
             if ema is None:
@@ -278,6 +325,7 @@ def run(cfg: TrainConfig) -> dict:
                 st.losses += s1.losses
                 st.evals += s1.evals
                 st.best, st.stopped, st.stop_index = s1.best, s1.stopped, s1.stop_index
+                st.plateau = s1.plateau
             done += k
             if cfg.keep_best and s1.stopped:  # the device's rule stopped and the host has seen it
                 done += s1.steps // max(1, tr.steps_per_epoch()) - k  # (the epochs this segment really ran)
@@ -319,6 +367,13 @@ def run(cfg: TrainConfig) -> dict:
             jlog({"event": "ema", "decay": es["decay"], "warmup": es["warmup"], "t": es["t"],
                   "adopted": bool(cfg.use_ema)})
             out.update(ema_t=es["t"])
+        if plateau is not None:
+            ps = tr.plateau_state()
+            log0(rank, f"Plateau rule ({plateau.monitor}): scale {ps['scale']:.10g} after {ps['reductions']} "
+                       f"reduction(s) in {ps['evals']} evaluation(s), best {ps['best']:.10g}")
+            jlog({"event": "plateau", "scale": ps["scale"], "reductions": ps["reductions"], "evals": ps["evals"],
+                  "best": ps["best"], "last_reduced_index": ps["last_reduced_index"], "monitor": plateau.monitor})
+            out.update(lr_scale=ps["scale"], lr_reductions=ps["reductions"])
         if tr.profiler is not None:
             phases = tr.profiler.summary()
             out["profile"] = phases

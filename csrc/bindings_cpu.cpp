@@ -13,6 +13,7 @@
 #include "mlp/affine.h"
 #include "mlp/augment.h"
 #include "mlp/best.h"
+#include "mlp/plateau.h"
 #include "mlp/clip.h"
 #include "mlp/ema.h"
 #include "mlp/shuffle.h"
@@ -422,6 +423,49 @@ PYBIND11_MODULE(_cpu, m) {
     cme::best_store(out.mutable_data(), cme::best_start());
     return out;
   });
+
+  // reduce on plateau (csrc/mlp/plateau.h, the header the kernels compile): one decision.  record = the 8 doubles
+  // {evals, best, bad, cooldown_left, scale, reductions, last_metric, last_reduced_index}; rule = (monitor, factor,
+  // patience, threshold, threshold_mode, cooldown, min_factor, eps) with monitor 0 = loss (min), 1 = accuracy (max) and
+  // threshold_mode 0 = rel, 1 = abs; triples = [R][3] doubles {n, correct, loss_sum}, summed in rank order.  Returns
+  // (the advanced record, reduced).  plateau_decide_metric takes the metric itself.  plateau_rate: lr_t * scale.
+  {
+    auto rule_of = [](py::tuple r) {
+      if (r.size() != 8) throw std::invalid_argument("plateau: rule = (monitor, factor, patience, threshold, threshold_mode, cooldown, min_factor, eps)");
+      cme::PlateauRule q{r[0].cast<int>(), r[1].cast<double>(), r[2].cast<int>(), r[3].cast<double>(),
+                         r[4].cast<int>(), r[5].cast<int>(), r[6].cast<double>(), r[7].cast<double>()};
+      if (!cme::plateau_rule_ok(q)) throw std::invalid_argument("plateau: rule out of range");
+      return q;
+    };
+    auto decide = [](f64arr record, const cme::PlateauRule& rule, double metric) {
+      if (record.size() != cme::kPlateauRecWords) throw std::invalid_argument("plateau_decide: a record of 8 doubles");
+      cme::PlateauRecord rec = cme::plateau_load(record.data());
+      const bool reduced = cme::plateau_decide(rec, rule, metric);
+      py::array_t<double> out(cme::kPlateauRecWords);
+      cme::plateau_store(out.mutable_data(), rec);
+      return py::make_tuple(out, reduced);
+    };
+    m.def(
+        "plateau_decide",
+        [rule_of, decide](f64arr record, py::tuple rule, f64arr triples) {
+          if (triples.ndim() != 2 || triples.shape(0) < 1 || triples.shape(1) != 3)
+            throw std::invalid_argument("plateau_decide: triples [R][3], R >= 1");
+          const cme::PlateauRule q = rule_of(rule);
+          return decide(record, q, cme::best_metric_of(triples.data(), (int)triples.shape(0), q.monitor));
+        },
+        py::arg("record"), py::arg("rule"), py::arg("triples"));
+    m.def(
+        "plateau_decide_metric",
+        [rule_of, decide](f64arr record, py::tuple rule, double metric) { return decide(record, rule_of(rule), metric); },
+        py::arg("record"), py::arg("rule"), py::arg("metric"));
+    m.def("plateau_start", [](int monitor) {
+      py::array_t<double> out(cme::kPlateauRecWords);
+      cme::plateau_store(out.mutable_data(), cme::plateau_start(monitor));
+      return out;
+    }, py::arg("monitor") = 0);
+    m.def("plateau_rate", &cme::plateau_rate, py::arg("lr_t"), py::arg("scale"));
+    m.attr("plateau_scale_word") = cme::kPlateauScaleWord;
+  }
 
   // the per-epoch shuffle's order (csrc/mlp/shuffle.h, the header the gather kernel compiles): sample i of the
   // shuffled set is source sample perm[i]; key = the iteration counter at the epoch start

@@ -15,6 +15,7 @@
 #include "mlp/mlp_split.h"
 #include "mlp/mlp_step.h"
 #include "mlp/best.h"
+#include "mlp/plateau.h"
 #include "mlp/clip.h"
 #include "mlp/ema.h"
 #include "mlp/optim.h"
@@ -399,13 +400,14 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
   // the extended apply launch: optim_step's arguments by the same names, plus kind 2 = the stateless sgd rule (s1 = 0),
   // window = the schedule window {t0, n, f[0 .. n)} with room for wcap factors (0: the rate is lr), partials / npart /
   // clip_norm = the sum-of-squares partials of grad_sumsq and the threshold (clip_norm 0: no clipping), last = the
-  // 4-double last-update record {t, lr_t, grad_norm, clip_coef} (0: none)
+  // 4-double last-update record {t, lr_t, grad_norm, clip_coef} (0: none), plateau = the scale word of a plateau record
+  // (0: none; trailing, so every earlier call keeps its signature)
   m.def(
       "optim_apply",
       [](int dt, int kind, double lr, double mu, int nesterov, double beta1, double beta2, double eps,
          uintptr_t params, uintptr_t grads, uintptr_t s1, uintptr_t s2, int64_t count, uintptr_t planes, int np,
          int64_t w1n, uintptr_t status, uintptr_t rec, int nrec, uintptr_t window, int wcap, uintptr_t partials,
-         int npart, double clip_norm, uintptr_t last, uintptr_t s) {
+         int npart, double clip_norm, uintptr_t last, uintptr_t s, uintptr_t plateau) {
         cme::OptimArgs a;
         a.dtype = dt; a.kind = kind;
         a.h.lr = lr; a.h.mu = mu; a.h.nesterov = nesterov; a.h.beta1 = beta1; a.h.beta2 = beta2; a.h.eps = eps;
@@ -414,14 +416,14 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
         a.rec = P<double>(rec); a.nrec = nrec;
         cme::OptimExt x;
         x.window = P<const double>(window); x.wcap = wcap; x.partials = P<const double>(partials); x.npart = npart;
-        x.clip_norm = clip_norm; x.last = P<double>(last);
+        x.clip_norm = clip_norm; x.last = P<double>(last); x.plateau = P<const double>(plateau);
         cme::mlp_optim_apply(a, x, P<void>(s));
       },
       py::arg("dt"), py::arg("kind"), py::arg("lr"), py::arg("mu"), py::arg("nesterov"), py::arg("beta1"),
       py::arg("beta2"), py::arg("eps"), py::arg("params"), py::arg("grads"), py::arg("s1"), py::arg("s2"),
       py::arg("count"), py::arg("planes") = 0, py::arg("np") = 0, py::arg("w1n") = 0, py::arg("status") = 0,
       py::arg("rec") = 0, py::arg("nrec") = 0, py::arg("window") = 0, py::arg("wcap") = 0, py::arg("partials") = 0,
-      py::arg("npart") = 0, py::arg("clip_norm") = 0.0, py::arg("last") = 0, py::arg("stream") = 0);
+      py::arg("npart") = 0, py::arg("clip_norm") = 0.0, py::arg("last") = 0, py::arg("stream") = 0, py::arg("plateau") = 0);
   // gradient-norm clipping (csrc/mlp/clip.h): the sum of squares of the segments [(offset, size), ...] of the bucket
   // (`arena` elements) into clip_grid(sum of sizes) partials
   m.def("clip_grid", &cme::clip_grid, py::arg("count"));
@@ -460,6 +462,22 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
         cme::mlp_best_pack(P<const unsigned long long>(slot), P<double>(rows), R, rank, P<void>(s));
       },
       py::arg("slot"), py::arg("rows"), py::arg("R"), py::arg("rank"), py::arg("stream") = 0);
+  // reduce on plateau (csrc/mlp/plateau.h): one launch behind an evaluation advances the one record of 8 doubles;
+  // exactly one of slot (a stats slot of eval.h) and rows ([R][3] doubles) is non-zero.  plateau_scale_word: the index
+  // of the record's word the apply launch reads
+  m.attr("plateau_scale_word") = cme::kPlateauScaleWord;
+  m.def(
+      "mlp_plateau",
+      [](int monitor, double factor, int patience, double threshold, int threshold_mode, int cooldown,
+         double min_factor, double eps, uintptr_t rec, uintptr_t slot, uintptr_t rows, int R, uintptr_t s) {
+        cme::PlateauArgs a;
+        a.rule = {monitor, factor, patience, threshold, threshold_mode, cooldown, min_factor, eps};
+        a.rec = P<double>(rec); a.slot = P<const unsigned long long>(slot); a.rows = P<const double>(rows); a.R = R;
+        cme::mlp_plateau(a, P<void>(s));
+      },
+      py::arg("monitor"), py::arg("factor"), py::arg("patience"), py::arg("threshold"), py::arg("threshold_mode"),
+      py::arg("cooldown"), py::arg("min_factor"), py::arg("eps"), py::arg("rec"), py::arg("slot") = 0,
+      py::arg("rows") = 0, py::arg("R") = 1, py::arg("stream") = 0);
   // the exponential moving average of the parameters (csrc/mlp/ema.h): one launch behind every applied update; rec =
   // ema_grid(count) records of 4 doubles; status (the parameter dtype) and err (int32) are the optional skip words
   m.def("ema_grid", &cme::ema_grid, py::arg("count"));

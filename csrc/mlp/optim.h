@@ -174,7 +174,9 @@ __host__ __device__ inline void adam_update(T& p, T& m, T& s, T g, const AdamCoe
 //   clip_norm > 0: partials = the npart = clip_grid(...) partial sums of squares the launch before this one left
 //     (clip.h); every workgroup combines them in the header's order and scales the gradient it reads by T(coef) when
 //     coef < 1;
-//   last: 4 doubles {t, lr_t, grad_norm, clip_coef} written by workgroup 0 (NaN, 1 without clipping), or null.
+//   last: 4 doubles {t, lr_t, grad_norm, clip_coef} written by workgroup 0 (NaN, 1 without clipping), or null;
+//   plateau: the `scale` word of a plateau record (plateau.h), or null: lr_t = plateau_rate(lr_t, *plateau) after the
+//     window lookup, so `last` reports the rate that was used.
 // mlp_optim_step is the launch as it stood: the same kernel signature, the same code, the same bits.
 // Plain vector stores only; no workgroup waits for another.
 struct OptimArgs {
@@ -199,6 +201,7 @@ struct OptimExt {
   int npart = 0;
   double clip_norm = 0.0;
   double* last = nullptr;
+  const double* plateau = nullptr;
 };
 constexpr int kOptimLastWords = 4;
 constexpr int kOptimRecWords = 4;  // doubles per record (32 bytes)

@@ -24,12 +24,15 @@
 //            <= 64 checked by the launcher) and runs clip.h's lane tree; thread 0 forms norm, coef and T(coef);
 //   window   thread 0 reads t BEFORE advancing it and the factor at the clamped index (optim.h window_index: no index
 //            leaves the buffer of wcap factors whatever it holds), lr_t = h.lr * f[i], and derives the scalars from it;
+//   plateau  thread 0 multiplies lr_t by the scale word of the plateau record (plateau.h plateau_rate) when one is set:
+//            one 8-byte load; the decision launch (plateau.hip) is the word's only writer, ordered on the stream;
 //   last     thread 0 of workgroup 0 stores {t, lr_t, norm, coef}.
 //   Every thread multiplies the gradient elements it reads by T(coef) when the update is clipped (coef < 1).
 // optim_kernel keeps its signature and, with EXT = 0, its code as it stood.  Measured: bench/clip_cost.py, docs/PERFORMANCE.md "Schedules and clipping".
 #include "optim.h"
 
 #include "clip.h"
+#include "plateau.h"
 
 #include "common/hip_common.h"
 
@@ -91,10 +94,15 @@ __device__ __forceinline__ void optim_body(const OptimArgs& a, const OptimExt& x
   }
   if (threadIdx.x == 0) {
     double* r = a.rec + static_cast<int64_t>(blockIdx.x) * kOptimRecWords;
+    double pscale = 1.0;
+    if constexpr (EXT) {
+      if (x.plateau) pscale = *x.plateau;  // (issued with the record's loads, not behind the window lookup)
+    }
     OptimCounter c{r[0], r[1], r[2]};
     OptimHyper h = a.h;
     if constexpr (EXT) {
       if (x.window) h.lr = window_rate(a.h.lr, x.window, x.wcap, c.t);
+      if (x.plateau) h.lr = plateau_rate(h.lr, pscale);
       ClipCoef cc{__builtin_nan(""), 1.0, 0};
       if (x.clip_norm > 0.0) cc = clip_coef(sumsq, x.clip_norm);
       s_scale = static_cast<T>(cc.coef);
@@ -279,6 +287,7 @@ void mlp_optim_apply(const OptimArgs& a, const OptimExt& x, void* stream) {
   CME_REQUIRE(x.clip_norm >= 0.0, "mlp_optim_apply: clip_norm must be >= 0 (0: no clipping)");
   CME_REQUIRE(!(x.clip_norm > 0.0) || (x.partials && x.npart >= 1 && x.npart <= kClipMaxGrid),
               "mlp_optim_apply: clipping needs 1 .. 64 sum-of-squares partials");
+  CME_REQUIRE(al(x.plateau, 8), "mlp_optim_apply: the plateau scale word must be 8-byte aligned");
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (a.dtype == 0) launch_kind<float, 1>(a, x, st);
   else launch_kind<double, 1>(a, x, st);
