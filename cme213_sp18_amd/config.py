@@ -50,6 +50,9 @@ class TrainConfig:
     num_classes: int = 10       # --classes: output classes (up to 64); labels must lie in [0, classes)
     eval_every: int = 0         # --eval-every N: evaluate the resident dev split on the device every N epochs (dp)
     shuffle_seed: int | None = None  # --shuffle-seed S: reshuffle the resident training set on the device every epoch
+    balance_classes: bool = False  # --balance-classes: draw every epoch with replacement, every class equally often
+    sample_weights: str = ""    # --sample-weights FILE.npy: ... with per-sample weights (sampling.Weighted)
+    sampler_seed: int = 0       # --sampler-seed S
     augment_shift: int | None = None    # --augment-shift M: move every training image by up to M pixels per epoch
     augment_shift_y: int | None = None  # --augment-shift-y: the vertical bound (default: M)
     augment_seed: int = 0       # --augment-seed S
@@ -152,6 +155,20 @@ class TrainConfig:
         aug = Shift(self.augment_shift, self.augment_shift_y, h, w, self.augment_seed)
         aug.shape(self.H[0])
         return aug
+
+    @property
+    def sampler(self):
+        """The sampling.Balanced of --balance-classes or the sampling.Weighted of --sample-weights, or None."""
+        from .sampling import Balanced, Weighted
+
+        if self.balance_classes:
+            return Balanced(self.sampler_seed)
+        if self.sample_weights:
+            import numpy as np
+
+            return Weighted(np.load(self.sample_weights, allow_pickle=False), self.sampler_seed,
+                            source=self.sample_weights)
+        return None
 
     @property
     def augment_affine(self) -> bool:
@@ -273,6 +290,14 @@ def build_parser() -> argparse.ArgumentParser:
                     help="reshuffle the resident training set on the device before every epoch (sequential and "
                          "parallel run alike; the order depends on the seed and the iteration counter only, so "
                          "--resume continues the sequence); default: the loaded order every epoch")
+    ap.add_argument("--balance-classes", action="store_true", default=None,
+                    help="draw every epoch's N training samples with replacement on the device, each with weight "
+                         "1 / (its class's count), so that every class is seen equally often (sequential and parallel "
+                         "run alike; the draws depend on --sampler-seed and the iteration counter only, so --resume "
+                         "continues the sequence); not with --shuffle-seed")
+    ap.add_argument("--sample-weights", metavar="FILE.npy",
+                    help="the same with per-sample weights: a vector of one non-negative weight per training sample")
+    ap.add_argument("--sampler-seed", type=int, help="seed of the draws (default 0)")
     ap.add_argument("--augment-shift", type=int,
                     help="before every epoch move each training image by its own random (dx, dy), |dx| and |dy| <= M, "
                          "on the device (zeros move in; sequential and parallel run alike; the shifts depend on the "
@@ -433,6 +458,12 @@ def parse_config(argv=None) -> TrainConfig:
                  "it needs --parallel dp")
     if cfg.lr_plateau is not None and not cfg.eval_every > 0:
         ap.error("--lr-plateau acts on the evaluations: it needs --eval-every N > 0")
+    if cfg.balance_classes and cfg.sample_weights:
+        ap.error("--balance-classes and --sample-weights both choose the sampling weights: give one of them")
+    if (cfg.balance_classes or cfg.sample_weights) and cfg.shuffle_seed is not None:
+        ap.error("--balance-classes / --sample-weights draw in random order already: not with --shuffle-seed")
+    if "sampler_seed" in explicit and not (cfg.balance_classes or cfg.sample_weights):
+        ap.error("--sampler-seed needs --balance-classes or --sample-weights")
     if cfg.augment_shift is None and not cfg.augment_affine and not cfg.augment_elastic and any(
             k in explicit for k in ("augment_shift_y", "augment_seed", "image_shape")):
         ap.error("--augment-shift-y, --augment-seed and --image-shape need --augment-shift")
@@ -440,6 +471,7 @@ def parse_config(argv=None) -> TrainConfig:
         ap.error("--augment-table needs --augment-rotate, --augment-scale or --augment-shear")
     try:
         cfg.augment  # the image shape and the bounds (augment.Shift validates)
+        cfg.sampler  # (the weights file is read; sampling validates the seed)
         cfg.optim  # the hyper-parameters' ranges (optim.Optimizer validates)
         cfg.schedule
         cfg.ema_rule  # (optim.Ema validates the decay)
@@ -447,6 +479,6 @@ def parse_config(argv=None) -> TrainConfig:
         from .optim import resolve_policy
 
         resolve_policy(None, cfg.clip_norm)
-    except ValueError as ex:
+    except (ValueError, OSError) as ex:
         ap.error(str(ex))
     return cfg

@@ -121,7 +121,7 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
           outdir: str = "Outputs", shift: bool = True, ckpt_precision: int = 12, iter0: int = 0,
           shuffle_seed: int | None = None, optimizer=None, optim_state: dict | None = None, schedule=None,
           clip_norm: float | None = None, update_log: list | None = None, augment=None, ema=None,
-          ema_state: dict | None = None, lr_scale: float | None = None) -> list[float]:
+          ema_state: dict | None = None, lr_scale: float | None = None, sampler=None) -> list[float]:
     """Sequential fp64 minibatch SGD on the CPU -- the oracle (neural_network.cpp:219-279).
 
     ``optimizer``: an ``optim.Optimizer`` (None or ``Optimizer.sgd()``: the reference's plain update).  A stateful
@@ -150,6 +150,10 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
     An ``augment.Affine`` goes through ``apply_affine`` with the samples' table entries instead (csrc/mlp/affine.h):
     uint8 ``X`` is blended by the integer rule, as the trainers' resident bytes are, anything else in fp64.  An
     ``augment.Warp`` goes through ``apply_warp`` with the samples' lattice nodes besides (csrc/mlp/warp.h).
+
+    ``sampler`` (a ``sampling.Balanced`` / ``Weighted``; the parallel trainers' ``sampler=``; not together with
+    ``shuffle_seed``): every epoch runs on the rows ``sampler.draws(labels, iteration counter)`` -- a draw with
+    replacement (csrc/mlp/sample.h) -- and an augmentation is then keyed by the position in the epoch, not by the row.
 
     ``ema`` (an ``optim.Ema``; the parallel trainer's ``ema=``): after every update the parameters are folded into an
     average by the rule of csrc/mlp/ema.h.  ``ema_state`` -- ``optim.new_ema_state(nn)``: {"t": the count of averaged
@@ -216,8 +220,11 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
             raise ValueError("ema_state does not belong to this network")
         ema_t = np.array([float(est["t"])], np.float64)
         kw["ema"] = (float(ema.decay), bool(ema.warmup), est["avg"], ema_t)
+    from ..sampling import resolve as resolve_sampler
+
+    sampler = resolve_sampler(sampler, shuffle_seed)
     try:
-        if shuffle_seed is None and augment is None:
+        if shuffle_seed is None and augment is None and sampler is None:
             if rates is not None:
                 kw["rates"] = rates
             return list(cpu().train(*nn.params, X, labels, float(learning_rate), float(reg), int(epochs),
@@ -235,19 +242,22 @@ def train(nn: NeuralNetwork, X, labels, learning_rate: float, reg: float = 0.0, 
         for ep in range(int(epochs)):
             perm = (cpu().epoch_permutation(n, int(shuffle_seed), it) if shuffle_seed is not None
                     else np.arange(n, dtype=np.int32))
+            ids = perm  # what the augmentation rules hash: the loaded index, or with a sampler the position
+            if sampler is not None:
+                perm, ids = sampler.draws(labels, it), np.arange(n)
             if rates is not None:
                 kw["rates"] = np.ascontiguousarray(rates[ep * nb:(ep + 1) * nb])
             Xe = np.ascontiguousarray(X[perm])
             if augment is not None and affine:  # (csrc/mlp/affine.h: the sample's table entry, then its shift)
-                entries = augment.table()[epoch_transforms(n, augment, it)[perm]]
+                entries = augment.table()[epoch_transforms(n, augment, it)[ids]]
                 Xe = X_raw[perm] if X_raw is not None else Xe
                 if warp:  # (csrc/mlp/warp.h: the affine map with the field of the sample's nodes on top)
-                    Xe = _x64(apply_warp(Xe, epoch_shifts(n, augment, it)[perm], entries,
-                                         epoch_nodes(n, augment, it)[perm], augment, img_h, img_w))
+                    Xe = _x64(apply_warp(Xe, epoch_shifts(n, augment, it)[ids], entries,
+                                         epoch_nodes(n, augment, it)[ids], augment, img_h, img_w))
                 else:
-                    Xe = _x64(apply_affine(Xe, epoch_shifts(n, augment, it)[perm], entries, img_h, img_w))
+                    Xe = _x64(apply_affine(Xe, epoch_shifts(n, augment, it)[ids], entries, img_h, img_w))
             elif augment is not None:
-                Xe = apply_shifts(Xe, epoch_shifts(n, augment, it)[perm], img_h, img_w)
+                Xe = apply_shifts(Xe, epoch_shifts(n, augment, it)[ids], img_h, img_w)
             losses += cpu().train(*nn.params, Xe, np.ascontiguousarray(labels[perm]),
                                   float(learning_rate), float(reg), 1, int(batch_size), int(print_every),
                                   bool(debug), outdir, shift, int(ckpt_precision), it, **kw)

@@ -160,6 +160,9 @@ class MlpEngine:
         # {(grid, h, w), device int32 [h + w][5]} -- it shares the shifts, the transforms and the table above
         self.warp_launches = 0
         self._warp_axes = None
+        # sampling with replacement (enqueue_shuffle / enqueue_augment with a sampling policy): the uploaded alias table
+        # {policy, host uint32 [N][2], its device copy} -- None without a sampler: nothing allocated, nothing changed
+        self._sampler = None
         self._eval = None  # the resident validation set and its evaluation buffers (load_eval)
         self._normalize = False
         self.xscale = 1.0
@@ -323,7 +326,7 @@ class MlpEngine:
             self.XTw = self.XT.to(torch.bfloat16).contiguous()
         self.labels = torch.as_tensor(np.asarray(labels, dtype=np.int32)).to(self.device).contiguous()
         self.num_samples = int(self.X.shape[0])
-        self.X0 = self.labels0 = self._perm = self._shifts = self._transforms = None
+        self.X0 = self.labels0 = self._perm = self._shifts = self._transforms = self._sampler = None
         if keep_source:
             # the loaded tensors become the (never written) source and the step reads fresh copies: on the CPU the
             # loaded ones may share memory with the caller's arrays, which a shuffle must not rewrite
@@ -336,20 +339,64 @@ class MlpEngine:
         self.refresh_shadow()
 
     # ------------------------------------------------------- per-epoch shuffle
-    def enqueue_shuffle(self, seed: int, key: int) -> None:
+    def enqueue_shuffle(self, seed: int, key: int, sampler=None) -> None:
         """Rewrite every resident layout (X, labels, XT, Xs, Xw, XTw) in place so that sample i is SOURCE sample
         perm[i], perm = epoch_permutation(N, seed, key) (csrc/mlp/shuffle.h; seed and key are unsigned 32-bit, packed
         as (seed << 32) ^ key).  Always gathers from the pristine copy, never from the previous order, so the order
         depends on (seed, key) alone.  On the current stream; no sync, no read-back, no allocation on the hip backend:
-        the buffers keep their addresses, so a bound MlpStep and every captured graph stay valid."""
-        self._shuffle(int(seed), int(key), False)
+        the buffers keep their addresses, so a bound MlpStep and every captured graph stay valid.
+
+        With ``sampler`` (a sampling.Balanced / Weighted; ``seed`` is then not used) perm[i] is a draw with replacement
+        instead: perm = sampler.draws(loaded labels, key) (csrc/mlp/sample.h), by the same one launch with the alias
+        table's address; the table is uploaded on first use (prepare_sampler: before a capture begins)."""
+        self._shuffle(int(seed), int(key), False, sampler)
+
+    def prepare_sampler(self, sampler) -> None:
+        """What a gather with ``sampler`` needs on the device, now: the alias table of the policy's weights for the
+        loaded labels (never rewritten).  The trainers call it from load(), so that no allocation and no upload happens
+        inside a capture.  An engine serves ONE policy per load_dataset(): a captured graph holds the table's address,
+        so another policy is refused (RuntimeError) rather than the table replaced under it; load the set again to
+        change it.  Raises ValueError for weights the rule refuses."""
+        if sampler is None or self.X is None or self.num_samples == 0:
+            return
+        if self.labels0 is None:
+            raise RuntimeError("no pristine copy of the training set: load_dataset(..., keep_source=True) first")
+        if self._sampler is not None:
+            if self._sampler[0] is sampler or self._sampler[0] == sampler:
+                return
+            raise RuntimeError(f"this engine already samples with {self._sampler[0]!r}: one policy per "
+                               "load_dataset() (a captured graph holds its table's address); load the set again "
+                               f"to sample with {sampler!r}")
+        table = sampler.table(self.labels0.cpu().numpy())
+        if table.shape != (self.num_samples, 2):
+            raise ValueError(f"the sampler's table is {table.shape}, the training set has {self.num_samples} samples")
+        dev = torch.from_numpy(table.view(np.int32).copy()).to(self.device).contiguous()  # (the bits of the uint32 pairs)
+        self._sampler = (sampler, table, dev)
+
+    def _sampler_kw(self, sampler) -> dict:
+        """The gather launchers' trailing arguments for ``sampler`` (nothing without one: the call is today's)."""
+        if sampler is None:
+            return {}
+        self.prepare_sampler(sampler)
+        return {"sample_table": self._sampler[2].data_ptr(), "sample_seed": sampler.seed}
+
+    def _host_order(self, key: int, shuffle_seed, sampler):
+        """(perm, ids) of the torch backend's gathers: the source row of every resident sample, and the index the
+        augmentation rules hash for it -- the source row, or with a sampler the destination."""
+        N = self.num_samples
+        if sampler is not None:
+            self.prepare_sampler(sampler)
+            return cpu().epoch_draws(N, sampler.seed, key, self._sampler[1]), np.arange(N)
+        perm = (np.arange(N, dtype=np.int32) if shuffle_seed is None
+                else cpu().epoch_permutation(N, int(shuffle_seed), key))
+        return perm, perm
 
     def unshuffle(self) -> None:
         """The order of load_dataset() again -- and, after an augmentation, its pixels: shifts() is zero again."""
         self._shuffle(0, 0, True)
 
     # ------------------------------------------------ per-epoch augmentation
-    def enqueue_augment(self, aug, key: int, shuffle_seed: int | None = None) -> None:
+    def enqueue_augment(self, aug, key: int, shuffle_seed: int | None = None, sampler=None) -> None:
         """enqueue_shuffle with the images moved on the way (augment.Shift; csrc/mlp/augment.h): every resident layout
         is rewritten in place from the pristine rows so that sample i is SOURCE sample perm[i] -- perm =
         epoch_permutation(N, shuffle_seed, key), or the loaded order without a seed -- shifted by
@@ -363,13 +410,19 @@ class MlpEngine:
 
         With an augment.Warp every source position of that resampling is moved by the field of the sample's lattice
         epoch_nodes(...)[perm[i]] (csrc/mlp/warp.h) by one launch of the warping gather (csrc/mlp/warp.hip) instead;
-        its axis tables are uploaded next to the table."""
+        its axis tables are uploaded next to the table.
+
+        With ``sampler`` (a sampling policy; no ``shuffle_seed`` then) perm is the epoch's draws with replacement
+        (enqueue_shuffle), and the shift, the table entry and the lattice are those of index i, the DESTINATION, not of
+        perm[i]: a row drawn many times gets a different augmentation at each of its places."""
         from ..augment import Affine, Warp
 
+        if sampler is not None and shuffle_seed is not None:
+            raise ValueError("sampler and shuffle_seed together: two orders would be ambiguous")
         if isinstance(aug, Warp):
-            return self._enqueue_warp(aug, int(key), shuffle_seed)
+            return self._enqueue_warp(aug, int(key), shuffle_seed, sampler)
         if isinstance(aug, Affine):
-            return self._enqueue_affine(aug, int(key), shuffle_seed)
+            return self._enqueue_affine(aug, int(key), shuffle_seed, sampler)
         key, seed = int(key), 0 if shuffle_seed is None else int(shuffle_seed)
         ready = self._gather_ready(seed, key)
         N, P = self.num_samples, self.P
@@ -382,12 +435,13 @@ class MlpEngine:
             self._transforms.zero_()
         if self.backend == "hip":
             self._gather_launch(hip().mlp_augment, self._shifts.data_ptr(), N, P, self.X.element_size(), h, w,
-                                aug.max_dx, aug.max_dy, aug.seed, key, int(shuffle_seed is not None), seed)
+                                aug.max_dx, aug.max_dy, aug.seed, key, int(shuffle_seed is not None), seed,
+                                **self._sampler_kw(sampler))
             self.augment_launches += 1
             return
         with torch.no_grad():
-            perm = (np.arange(N, dtype=np.int32) if shuffle_seed is None else cpu().epoch_permutation(N, seed, key))
-            shifts = cpu().epoch_shifts(N, aug.seed, key, aug.max_dx, aug.max_dy)[perm]
+            perm, ids = self._host_order(key, shuffle_seed, sampler)
+            shifts = cpu().epoch_shifts(N, aug.seed, key, aug.max_dx, aug.max_dy)[ids]
             self._perm.copy_(torch.from_numpy(perm))
             self._shifts.copy_(torch.from_numpy(shifts))
             # the rule moves bytes (zero fill = all-zero bits): the rows go through the host as same-size integers
@@ -423,7 +477,7 @@ class MlpEngine:
                 self._warp_axes = ((aug.grid, h, w),
                                    torch.from_numpy(aug.axes(h, w).copy()).to(self.device).contiguous())
 
-    def _enqueue_warp(self, aug, key: int, shuffle_seed: int | None) -> None:
+    def _enqueue_warp(self, aug, key: int, shuffle_seed: int | None, sampler=None) -> None:
         seed = 0 if shuffle_seed is None else int(shuffle_seed)
         ready = self._gather_ready(seed, key)
         N, P = self.num_samples, self.P
@@ -439,14 +493,14 @@ class MlpEngine:
             self._gather_launch(hip().mlp_warp, self._shifts.data_ptr(), self._transforms.data_ptr(),
                                 table.data_ptr(), int(table.shape[0]), kind, axes.data_ptr(), aug.grid[0], aug.grid[1],
                                 aug.bound, N, P, self.X.element_size(), h, w, aug.max_dx, aug.max_dy, aug.seed, key,
-                                int(shuffle_seed is not None), seed)
+                                int(shuffle_seed is not None), seed, **self._sampler_kw(sampler))
             self.warp_launches += 1
             return
         with torch.no_grad():
-            perm = (np.arange(N, dtype=np.int32) if shuffle_seed is None else cpu().epoch_permutation(N, seed, key))
-            shifts = cpu().epoch_shifts(N, aug.seed, key, aug.max_dx, aug.max_dy)[perm]
-            index = cpu().epoch_transforms(N, aug.seed, key, aug.table_size)[perm]
-            nodes = np.ascontiguousarray(cpu().epoch_nodes(N, aug.seed, key, aug.nodes, aug.bound)[perm])
+            perm, ids = self._host_order(key, shuffle_seed, sampler)
+            shifts = cpu().epoch_shifts(N, aug.seed, key, aug.max_dx, aug.max_dy)[ids]
+            index = cpu().epoch_transforms(N, aug.seed, key, aug.table_size)[ids]
+            nodes = np.ascontiguousarray(cpu().epoch_nodes(N, aug.seed, key, aug.nodes, aug.bound)[ids])
             self._perm.copy_(torch.from_numpy(perm))
             self._shifts.copy_(torch.from_numpy(shifts))
             self._transforms.copy_(torch.from_numpy(index))
@@ -458,7 +512,7 @@ class MlpEngine:
             self.labels.copy_(self.labels0.index_select(0, self._perm.long()))
             self._rebuild_from_rows()
 
-    def _enqueue_affine(self, aug, key: int, shuffle_seed: int | None) -> None:
+    def _enqueue_affine(self, aug, key: int, shuffle_seed: int | None, sampler=None) -> None:
         seed = 0 if shuffle_seed is None else int(shuffle_seed)
         ready = self._gather_ready(seed, key)
         N, P = self.num_samples, self.P
@@ -473,13 +527,14 @@ class MlpEngine:
             table = self._affine_table[1]
             self._gather_launch(hip().mlp_affine, self._shifts.data_ptr(), self._transforms.data_ptr(),
                                 table.data_ptr(), int(table.shape[0]), kind, N, P, self.X.element_size(), h, w,
-                                aug.max_dx, aug.max_dy, aug.seed, key, int(shuffle_seed is not None), seed)
+                                aug.max_dx, aug.max_dy, aug.seed, key, int(shuffle_seed is not None), seed,
+                                **self._sampler_kw(sampler))
             self.affine_launches += 1
             return
         with torch.no_grad():
-            perm = (np.arange(N, dtype=np.int32) if shuffle_seed is None else cpu().epoch_permutation(N, seed, key))
-            shifts = cpu().epoch_shifts(N, aug.seed, key, aug.max_dx, aug.max_dy)[perm]
-            index = cpu().epoch_transforms(N, aug.seed, key, aug.table_size)[perm]
+            perm, ids = self._host_order(key, shuffle_seed, sampler)
+            shifts = cpu().epoch_shifts(N, aug.seed, key, aug.max_dx, aug.max_dy)[ids]
+            index = cpu().epoch_transforms(N, aug.seed, key, aug.table_size)[ids]
             self._perm.copy_(torch.from_numpy(perm))
             self._shifts.copy_(torch.from_numpy(shifts))
             self._transforms.copy_(torch.from_numpy(index))
@@ -521,7 +576,8 @@ class MlpEngine:
 
     def permutation(self) -> torch.Tensor:
         """The current order as a device int32 tensor: resident sample i is loaded sample permutation()[i] (the
-        identity before any shuffle)."""
+        identity before any shuffle).  After a gather with a sampler these are the epoch's draws -- the source row of
+        every resident sample -- and no permutation: rows may repeat and rows may be missing."""
         if self._perm is not None:
             return self._perm
         if self.X is None:
@@ -539,14 +595,14 @@ class MlpEngine:
             raise ValueError("shuffle seed and key must be in [0, 2^32)")
         return self.num_samples != 0
 
-    def _gather_launch(self, launch, *rest) -> None:
+    def _gather_launch(self, launch, *rest, **sampler_kw) -> None:
         """hip().mlp_shuffle / mlp_augment on the current stream: the pristine source, the resident layouts and the
-        order as device addresses (0: a layout this engine does not hold), then ``rest``."""
+        order as device addresses (0: a layout this engine does not hold), then ``rest`` (and a sampler's table)."""
         held = (self.X0, self.labels0, self.X, self.labels, self.XT, self.Xs, self.Xw, self.XTw, self._perm)
         launch(*(t.data_ptr() if t is not None else 0 for t in held), *rest,
-               stream=torch.cuda.current_stream(self.device).cuda_stream)
+               stream=torch.cuda.current_stream(self.device).cuda_stream, **sampler_kw)
 
-    def _shuffle(self, seed: int, key: int, identity: bool) -> None:
+    def _shuffle(self, seed: int, key: int, identity: bool, sampler=None) -> None:
         if not self._gather_ready(seed, key):
             return
         N, P = self.num_samples, self.P
@@ -555,11 +611,12 @@ class MlpEngine:
         if self._transforms is not None:
             self._transforms.zero_()
         if self.backend == "hip":
-            self._gather_launch(hip().mlp_shuffle, N, P, self.X.element_size(), seed, key, int(identity))
+            self._gather_launch(hip().mlp_shuffle, N, P, self.X.element_size(), seed, key, int(identity),
+                                **self._sampler_kw(sampler))
             self.shuffle_launches += 1
             return
         with torch.no_grad():
-            perm = (np.arange(N, dtype=np.int32) if identity else cpu().epoch_permutation(N, seed, key))
+            perm = self._host_order(key, None if identity else seed, sampler)[0]
             self._perm.copy_(torch.from_numpy(perm))
             idx = self._perm.long()
             self.X.copy_(self.X0.index_select(0, idx))

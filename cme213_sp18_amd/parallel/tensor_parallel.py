@@ -47,7 +47,7 @@ class TensorParallelTrainer:
     def __init__(self, nn, comm: Communicator | None = None, device=None, dtype: str = "f32",
                  batch_size: int = 800, backend: str = "hip", shift: bool = True, normalize: bool = False,
                  path: str = "auto", allreduce: str = "auto", shuffle_seed: int | None = None, optimizer=None,
-                 schedule=None, clip_norm=None, augment=None, ema=None, plateau=None):
+                 schedule=None, clip_norm=None, augment=None, ema=None, plateau=None, sampler=None):
         from ..optim import resolve
 
         # the shard's update stays inside its weight-gradient launch (plain SGD); the stateful rules are
@@ -68,6 +68,9 @@ class TensorParallelTrainer:
         self.nn = nn
         self.shuffle_seed = None if shuffle_seed is None else int(shuffle_seed)  # (DataParallelTrainer's)
         self.augment = augment  # an augment.Shift or None (DataParallelTrainer's)
+        from ..sampling import resolve as resolve_sampler
+
+        self.sampler = resolve_sampler(sampler, shuffle_seed)  # a sampling policy or None (DataParallelTrainer's)
         self.comm = comm or NullComm()
         self.R, self.rank = self.comm.world_size, self.comm.rank
         P, H, C = nn.H
@@ -186,8 +189,10 @@ class TensorParallelTrainer:
         if self.augment is not None:
             self.augment.shape(self.engine.P)  # (raises when the image shape or the bounds do not fit)
         self.engine.load_dataset(x_train, y_train, normalize=self.normalize,
-                                 keep_source=self.shuffle_seed is not None or self.augment is not None)
+                                 keep_source=(self.shuffle_seed is not None or self.augment is not None
+                                              or self.sampler is not None))
         self.N = self.engine.num_samples
+        self.engine.prepare_sampler(self.sampler)  # its table goes to the device once, here: never inside a capture
         if isinstance(self.augment, (Affine, Warp)):  # its tables go to the device once, here: never inside a capture
             self.engine.prepare_augment(self.augment)
 
@@ -337,6 +342,8 @@ class TensorParallelTrainer:
         stats = TrainStats()
         plan = self.epoch_plan()
         seed = self.shuffle_seed if shuffle_seed is None else int(shuffle_seed)
+        if self.sampler is not None and seed is not None:
+            raise ValueError("sampler and shuffle_seed together: two orders would be ambiguous")
         dev = self.engine.device
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
@@ -346,9 +353,9 @@ class TensorParallelTrainer:
             if fault is not None and fault[0] == self.rank and self.iter <= fault[1] < self.iter + len(plan.steps):
                 raise FaultInjected(f"injected fault on rank {self.rank} at step {fault[1]}")
             if self.augment is not None:  # the augmenting gather in the shuffle's place (the same order)
-                self.engine.enqueue_augment(self.augment, self.iter, seed)
-            elif seed is not None:
-                self.engine.enqueue_shuffle(seed, self.iter)
+                self.engine.enqueue_augment(self.augment, self.iter, seed, sampler=self.sampler)
+            elif seed is not None or self.sampler is not None:  # (with a sampler: the epoch's draws, as in DP)
+                self.engine.enqueue_shuffle(seed or 0, self.iter, sampler=self.sampler)
             if print_every <= 0 and self.profiler is None:
                 self.run_plan(plan, lr, reg, use_graphs=self.use_graphs)
                 self.iter += len(plan.steps)

@@ -247,7 +247,7 @@ class DataParallelTrainer:
                  overlap_chunks: int = 0, fuse_allreduce: bool = True, executor: str = "auto",
                  grad_wire: str = "auto", fused_form: str = "auto", shuffle_seed: int | None = None,
                  optimizer=None, schedule=None, clip_norm=None, augment=None, ema=None,
-                 plateau=None):
+                 plateau=None, sampler=None):
         self.nn = nn
         # an exponential moving average of the parameters (optim.Ema; None: nothing allocated, nothing launched): one
         # more launch behind every applied update folds the parameters into a resident averaged arena, on every sync
@@ -290,6 +290,13 @@ class DataParallelTrainer:
         # load() keeps the pristine rows and train() enqueues the augmenting gather INSTEAD of the shuffle before each
         # epoch -- the order as above (the loaded one without a shuffle seed), every image moved by its own keyed shift
         self.augment = augment
+        # sampling with replacement (a sampling.Balanced / Weighted; None: nothing kept, nothing launched): load() keeps
+        # the pristine rows and uploads the alias table, and the gather train() enqueues before each epoch -- the
+        # shuffle's or the augmentation's, no further launch -- takes every sample's source row from the keyed draws of
+        # (sampler.seed, iteration counter at the epoch start) instead of an order.  Not together with shuffle_seed
+        from ..sampling import resolve as resolve_sampler
+
+        self.sampler = resolve_sampler(sampler, shuffle_seed)
         # how run_plan enqueues a plan: "auto" = the native C++ step loop (MlpStep.run_steps) for plans of
         # consecutive full batches on the fused paths (pure device work), else the captured HIP graph;
         # "graph" = always the graph; "eager" = Python step by step
@@ -589,8 +596,10 @@ class DataParallelTrainer:
         if self.augment is not None:
             self.augment.shape(self.engine.P)  # (raises when the image shape or the bounds do not fit)
         self.engine.load_dataset(x_train, y_train, normalize=self.normalize,
-                                 keep_source=self.shuffle_seed is not None or self.augment is not None)
+                                 keep_source=(self.shuffle_seed is not None or self.augment is not None
+                                              or self.sampler is not None))
         self.N = self.engine.num_samples
+        self.engine.prepare_sampler(self.sampler)  # its table goes to the device once, here: never inside a capture
         if isinstance(self.augment, (Affine, Warp)):  # its tables go to the device once, here: never inside a capture
             self.engine.prepare_augment(self.augment)
         self._graphs.clear()
@@ -1101,6 +1110,13 @@ class DataParallelTrainer:
         every rank forms the same pixels, and the validation set and predict() are never augmented.  Afterwards the
         set stays in the last epoch's state (engine.permutation(), engine.shifts()); step(start, ...) indexes it.
 
+        With ``sampler`` (the constructor's sampling.Balanced / Weighted; no shuffle_seed then) that same one gather
+        draws every sample's source row with replacement, keyed by (sampler.seed, iteration counter at the epoch
+        start): an epoch still holds N samples, a row may appear several times or not at all, and an augmentation is
+        then keyed by the resident index, so every copy of a row gets its own.  A recovered epoch repeats its draws,
+        train(2) + train(2) equals train(4), every rank forms the same set; the validation set and predict() are
+        never sampled.  engine.permutation() holds the last epoch's draws.
+
         With a schedule (the constructor's), the call reads the device's update count once, behind its start-of-call
         sync, and fills the schedule window for ``epochs * steps_per_epoch`` updates from there, steps_per_epoch =
         len(epoch_plan().steps): the apply launch looks its factor up on the device, so every epoch replays from the
@@ -1159,6 +1175,8 @@ class DataParallelTrainer:
         stats = TrainStats()
         plan = self.epoch_plan()
         seed = self.shuffle_seed if shuffle_seed is None else int(shuffle_seed)
+        if self.sampler is not None and seed is not None:
+            raise ValueError("sampler and shuffle_seed together: two orders would be ambiguous")
         err_file, own_file = diff_file, False
         if debug and self.rank == 0 and err_file is None:  # only rank 0 owns the diff file
             os.makedirs(outdir, exist_ok=True)
@@ -1228,9 +1246,9 @@ class DataParallelTrainer:
         def run_epoch(epoch: int) -> None:
             # (inside run_epoch: a recovered epoch restores self.iter and gets the same order and the same shifts)
             if self.augment is not None:
-                self.engine.enqueue_augment(self.augment, self.iter, seed)
-            elif seed is not None:
-                self.engine.enqueue_shuffle(seed, self.iter)
+                self.engine.enqueue_augment(self.augment, self.iter, seed, sampler=self.sampler)
+            elif seed is not None or self.sampler is not None:
+                self.engine.enqueue_shuffle(seed or 0, self.iter, sampler=self.sampler)
             if not host_needed:
                 maybe_fault(self.iter, len(plan.steps))
                 with self.roctx.range(f"epoch {epoch}"):

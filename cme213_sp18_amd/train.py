@@ -89,9 +89,11 @@ def run(cfg: TrainConfig) -> dict:
             aug_meta["table_checksum"] = f"{aug.table_checksum():016x}"
         elif aug_meta is not None and aug_meta["kind"] == "warp":  # (its axis tables are built in fp64 too)
             aug_meta["table_checksum"] = f"{aug.table_checksum(*aug.shape(cfg.H[0])):016x}"
+        smp = cfg.sampler  # a sampling.Balanced, a sampling.Weighted or None
         jlog({"event": "config", "world": world, "device": str(device), **placement, **{
             k: v for k, v in vars(cfg).items() if isinstance(v, (int, float, str, bool))},
             "augment": aug_meta,
+            "sampler": smp.to_meta() if smp is not None else None,
             "ema": cfg.ema_rule.as_meta() if cfg.ema_rule is not None else None,
             "plateau": cfg.plateau.as_meta() if cfg.plateau is not None else None})
         log0(rank, f"Number of processes = {world}")
@@ -110,6 +112,14 @@ def run(cfg: TrainConfig) -> dict:
         log0(rank, f"Loaded {ds.source}: train {ds.x_train.shape[0]}, dev {ds.x_dev.shape[0]}, "
                    f"test {ds.x_test.shape[0]} ({time.perf_counter() - t:.2f}s)")
         os.makedirs(cfg.outdir, exist_ok=True)
+        # what meta.json records of the sampler: the policy and a checksum of its alias table (built in fp64 on the
+        # host from this training split: other weights or another split must not silently change a resumed run)
+        smp_meta = None
+        if smp is not None:
+            try:
+                smp_meta = {**smp.to_meta(), "table_checksum": f"{smp.checksum(ds.y_train):016x}"}
+            except ValueError as ex:
+                raise SystemExit(f"error: {ex}")
         meta = {}
         opt = cfg.optim
         sched, clip = cfg.schedule, cfg.clip_norm
@@ -184,6 +194,18 @@ def run(cfg: TrainConfig) -> dict:
                            f"{meta['augment'].get('table_checksum')}, this run's has "
                            f"{aug_meta.get('table_checksum')} (another math library?): the epochs' transforms do not "
                            "continue the checkpoint's")
+            saved_smp = meta.get("sampler")
+            # (the checksum is compared apart; `source` is where the weights were read from, weights_checksum says
+            # which they are: the same file at another path is the same sampler)
+            strip = lambda m: ({k: v for k, v in m.items() if k not in ("table_checksum", "source")}  # noqa: E731
+                               if m else None)
+            if strip(saved_smp) != strip(smp_meta):
+                log0(rank, f"warning: the checkpoint was trained with sampler {strip(saved_smp)}, this run uses "
+                           f"{strip(smp_meta)}: the epochs' draws do not continue the checkpoint's")
+            elif smp_meta is not None and saved_smp.get("table_checksum") != smp_meta["table_checksum"]:
+                log0(rank, f"warning: the checkpoint's sampling table has checksum {saved_smp.get('table_checksum')}, "
+                           f"this run's has {smp_meta['table_checksum']} (other labels or weights?): the epochs' "
+                           "draws do not continue the checkpoint's")
         else:
             nn = NeuralNetwork(cfg.H)
         seq_nn = nn.copy()
@@ -202,7 +224,7 @@ def run(cfg: TrainConfig) -> dict:
                     seq_ema = {"t": ema_saved["t"], "avg": np.concatenate(
                         [np.asarray(a, np.float64).reshape(-1) for a in (W1a, b1a, W2a, b2a)])}
             seq_kw = dict(shuffle_seed=cfg.shuffle_seed, optimizer=opt, schedule=sched, clip_norm=clip, augment=aug,
-                          ema=ema, ema_state=seq_ema)
+                          ema=ema, ema_state=seq_ema, sampler=smp)
             if plateau is None:
                 mlp.train(seq_nn, xs, ds.y_train, cfg.learning_rate, cfg.reg, cfg.num_epochs, cfg.batch_size,
                           False, cfg.print_every, cfg.debug, cfg.outdir, cfg.softmax_shift, cfg.ckpt_precision,
@@ -254,14 +276,15 @@ def run(cfg: TrainConfig) -> dict:
                                        path=cfg.path,
                                        allreduce=tp_allreduce_mode(cfg.allreduce), shuffle_seed=cfg.shuffle_seed,
                                        optimizer=opt, schedule=sched, clip_norm=clip, augment=aug, ema=ema,
-                                       plateau=plateau)
+                                       plateau=plateau, sampler=smp)
             tr.use_graphs = cfg.use_graphs
         else:
             tr = DataParallelTrainer(nn, comm=comm, device=device, dtype=cfg.dtype, batch_size=cfg.batch_size,
                                      backend=backend, shift=cfg.softmax_shift, use_graphs=cfg.use_graphs,
                                      normalize=cfg.normalize, path=cfg.path, allreduce=cfg.allreduce,
                                      overlap_chunks=cfg.overlap_chunks, shuffle_seed=cfg.shuffle_seed, optimizer=opt,
-                                     schedule=sched, clip_norm=clip, augment=aug, ema=ema, plateau=plateau)
+                                     schedule=sched, clip_norm=clip, augment=aug, ema=ema, plateau=plateau,
+                                     sampler=smp)
             if opt_state is not None:
                 tr.engine.set_optim_state(opt_state)
             if plateau_saved is not None:
@@ -293,6 +316,7 @@ def run(cfg: TrainConfig) -> dict:
                                   "seed": cfg.seed, "dtype": cfg.dtype, "iter": tr.iter,
                                   "shuffle_seed": cfg.shuffle_seed,
                                   "augment": aug_meta,
+                                  **({"sampler": smp_meta} if smp_meta is not None else {}),
                                   **({"optimizer": opt.as_meta()} if opt.stateful else {}),
                                   **({"schedule": sched.as_meta()} if sched is not None else {}),
                                   **({"clip_norm": clip} if clip is not None else {}),

@@ -16,6 +16,7 @@
 #include "mlp/plateau.h"
 #include "mlp/clip.h"
 #include "mlp/ema.h"
+#include "mlp/sample.h"
 #include "mlp/shuffle.h"
 #include "mlp/warp.h"
 
@@ -480,6 +481,41 @@ PYBIND11_MODULE(_cpu, m) {
         return out;
       },
       py::arg("n"), py::arg("seed"), py::arg("key"));
+
+  // sampling with replacement (csrc/mlp/sample.h, the header the gather kernels compile).  The alias table of per-sample
+  // weights: uint32 [N][2] = {threshold, alias}, a pure function of the weights (fp64, no math library)
+  m.def(
+      "alias_table",
+      [](const py::array& weights) {
+        if (weights.ndim() != 1) throw std::invalid_argument("alias_table: the weights must be a vector [N]");
+        const f64arr w = f64arr::ensure(weights);
+        if (!w) throw std::invalid_argument("alias_table: the weights must be numbers");
+        const int64_t n = w.shape(0);
+        if (n < 1 || n >= (int64_t{1} << 31)) throw std::invalid_argument("alias_table: N must be in [1, 2^31)");
+        u32arr out({n, (int64_t)2});
+        cme::sample_alias_table(w.data(), n, out.mutable_data());
+        return out;
+      },
+      py::arg("weights"));
+  // ... and the draws of the epoch that starts at iteration counter `key`: sample i of the resident set is source
+  // sample draws[i] (rows may repeat), with the kernel's bits
+  m.def(
+      "epoch_draws",
+      [](int64_t n, uint32_t seed, uint32_t key, const u32arr& table) {
+        if (n < 1 || n > INT32_MAX) throw std::invalid_argument("epoch_draws: n must be in [1, 2^31)");
+        if (table.ndim() != 2 || table.shape(0) != n || table.shape(1) != 2)
+          throw std::invalid_argument("epoch_draws: the table must be uint32 [n][2]");
+        const uint32_t* t = table.data();
+        if (reinterpret_cast<uintptr_t>(t) & 7) throw std::invalid_argument("epoch_draws: the table must be 8-byte aligned");
+        for (int64_t i = 0; i < n; ++i)
+          if (t[2 * i + 1] >= (uint64_t)n) throw std::invalid_argument("epoch_draws: an alias is outside [0, n)");
+        py::array_t<int32_t> out(n);
+        int32_t* o = out.mutable_data();
+        const uint64_t k = cme::sample_key(seed, key);
+        for (int64_t i = 0; i < n; ++i) o[i] = (int32_t)cme::sample_draw((uint32_t)i, (uint32_t)n, k, t);
+        return out;
+      },
+      py::arg("n"), py::arg("seed"), py::arg("key"), py::arg("table"));
 
   // the augmentation's shifts (csrc/mlp/augment.h, the header the augmenting gather compiles): row i = (dx, dy) of
   // SOURCE sample i in the epoch that starts at iteration counter `key`

@@ -21,6 +21,7 @@
 #include "mlp/optim.h"
 #include "mlp/affine.h"
 #include "mlp/augment.h"
+#include "mlp/sample.h"
 #include "mlp/shuffle.h"
 #include "mlp/warp.h"
 #include "suite/suite_kernels.h"
@@ -83,8 +84,12 @@ py::dict form_dict(const cme::StepForm& p) {
 // device addresses, the shapes and the order
 cme::ShuffleArgs gather_args(uintptr_t X0, uintptr_t labels0, uintptr_t X, uintptr_t labels, uintptr_t XT,
                              uintptr_t Xs, uintptr_t Xw, uintptr_t XTw, uintptr_t perm, int N, int Pd, int es,
-                             uint64_t key, int identity) {
+                             uint64_t key, int identity, uintptr_t sample_table, uint32_t sample_seed,
+                             uint32_t iter) {
   cme::ShuffleArgs a;
+  // a sampler (csrc/mlp/sample.h): the alias table's device address (0: none) and the key of the epoch's draws
+  a.sample_table = P<const uint32_t>(sample_table);
+  a.sample_key = sample_table ? cme::sample_key(sample_seed, iter) : 0;
   a.X0 = P<const void>(X0); a.labels0 = P<const int>(labels0); a.X = P<void>(X); a.labels = P<int>(labels);
   a.XT = P<void>(XT); a.Xs = P<void>(Xs); a.Xw = P<void>(Xw); a.XTw = P<void>(XTw); a.perm = P<int>(perm);
   a.N = N; a.P = Pd; a.es = es; a.key = key; a.identity = identity;
@@ -304,24 +309,29 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
   m.def(
       "mlp_shuffle",
       [](uintptr_t X0, uintptr_t labels0, uintptr_t X, uintptr_t labels, uintptr_t XT, uintptr_t Xs, uintptr_t Xw,
-         uintptr_t XTw, uintptr_t perm, int N, int Pd, int es, uint32_t seed, uint32_t key, int identity, uintptr_t s) {
+         uintptr_t XTw, uintptr_t perm, int N, int Pd, int es, uint32_t seed, uint32_t key, int identity, uintptr_t s,
+         uintptr_t sample_table, uint32_t sample_seed) {
         cme::mlp_shuffle(gather_args(X0, labels0, X, labels, XT, Xs, Xw, XTw, perm, N, Pd, es,
-                                     cme::shuffle_key(seed, key), identity),
+                                     cme::shuffle_key(seed, key), identity, sample_table, sample_seed, key),
                          P<void>(s));
       },
       py::arg("X0"), py::arg("labels0"), py::arg("X"), py::arg("labels"), py::arg("XT"), py::arg("Xs"), py::arg("Xw"),
       py::arg("XTw"), py::arg("perm"), py::arg("N"), py::arg("P"), py::arg("es"), py::arg("seed"), py::arg("key"),
-      py::arg("identity") = 0, py::arg("stream") = 0);
+      py::arg("identity") = 0, py::arg("stream") = 0, py::arg("sample_table") = 0, py::arg("sample_seed") = 0);
   // the augmenting gather (csrc/mlp/augment.hip): mlp_shuffle's layouts, each image moved by its keyed (dx, dy);
-  // shuffled != 0: the order of shuffle_key(shuffle_seed, key), else the loaded order
+  // shuffled != 0: the order of shuffle_key(shuffle_seed, key), else the loaded order.  sample_table != 0 (all four
+  // gathers; csrc/mlp/sample.h): the draws of sample_key(sample_seed, key) through that alias table instead, and the
+  // augmentations keyed by the destination
   m.def(
       "mlp_augment",
       [](uintptr_t X0, uintptr_t labels0, uintptr_t X, uintptr_t labels, uintptr_t XT, uintptr_t Xs, uintptr_t Xw,
          uintptr_t XTw, uintptr_t perm, uintptr_t shifts, int N, int Pd, int es, int h, int w, int max_dx, int max_dy,
-         uint32_t aug_seed, uint32_t key, int shuffled, uint32_t shuffle_seed, uintptr_t s) {
+         uint32_t aug_seed, uint32_t key, int shuffled, uint32_t shuffle_seed, uintptr_t s, uintptr_t sample_table,
+         uint32_t sample_seed) {
         cme::AugmentArgs aa;
         aa.base = gather_args(X0, labels0, X, labels, XT, Xs, Xw, XTw, perm, N, Pd, es,
-                              cme::shuffle_key(shuffle_seed, key), shuffled ? 0 : 1);
+                              cme::shuffle_key(shuffle_seed, key), shuffled || sample_table ? 0 : 1, sample_table,
+                              sample_seed, key);
         aa.h = h; aa.w = w; aa.max_dx = max_dx; aa.max_dy = max_dy; aa.akey = cme::augment_key(aug_seed, key);
         aa.shifts = P<int>(shifts);
         cme::mlp_augment(aa, P<void>(s));
@@ -329,7 +339,8 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       py::arg("X0"), py::arg("labels0"), py::arg("X"), py::arg("labels"), py::arg("XT"), py::arg("Xs"), py::arg("Xw"),
       py::arg("XTw"), py::arg("perm"), py::arg("shifts"), py::arg("N"), py::arg("P"), py::arg("es"), py::arg("h"),
       py::arg("w"), py::arg("max_dx"), py::arg("max_dy"), py::arg("aug_seed"), py::arg("key"),
-      py::arg("shuffled") = 0, py::arg("shuffle_seed") = 0, py::arg("stream") = 0);
+      py::arg("shuffled") = 0, py::arg("shuffle_seed") = 0, py::arg("stream") = 0, py::arg("sample_table") = 0,
+      py::arg("sample_seed") = 0);
   // the affine gather (csrc/mlp/affine.hip): mlp_augment's arguments, each image resampled through its table entry
   // (table: int32 [T][4] on the device; kind: 0 uint8, 1 bf16, 2 f32, 3 f64; transforms: int32 [N] or 0)
   m.def(
@@ -337,11 +348,13 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       [](uintptr_t X0, uintptr_t labels0, uintptr_t X, uintptr_t labels, uintptr_t XT, uintptr_t Xs, uintptr_t Xw,
          uintptr_t XTw, uintptr_t perm, uintptr_t shifts, uintptr_t transforms, uintptr_t table, int T, int kind, int N,
          int Pd, int es, int h, int w, int max_dx, int max_dy, uint32_t aug_seed, uint32_t key, int shuffled,
-         uint32_t shuffle_seed, uintptr_t s) {
+         uint32_t shuffle_seed, uintptr_t s, uintptr_t sample_table,
+         uint32_t sample_seed) {
         cme::AffineArgs fa;
         cme::AugmentArgs& aa = fa.aug;
         aa.base = gather_args(X0, labels0, X, labels, XT, Xs, Xw, XTw, perm, N, Pd, es,
-                              cme::shuffle_key(shuffle_seed, key), shuffled ? 0 : 1);
+                              cme::shuffle_key(shuffle_seed, key), shuffled || sample_table ? 0 : 1, sample_table,
+                              sample_seed, key);
         aa.h = h; aa.w = w; aa.max_dx = max_dx; aa.max_dy = max_dy; aa.akey = cme::augment_key(aug_seed, key);
         aa.shifts = P<int>(shifts);
         fa.table = P<const int32_t>(table); fa.T = T; fa.kind = kind; fa.transforms = P<int>(transforms);
@@ -351,7 +364,8 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       py::arg("XTw"), py::arg("perm"), py::arg("shifts"), py::arg("transforms"), py::arg("table"), py::arg("T"),
       py::arg("kind"), py::arg("N"), py::arg("P"), py::arg("es"), py::arg("h"), py::arg("w"), py::arg("max_dx"),
       py::arg("max_dy"), py::arg("aug_seed"), py::arg("key"), py::arg("shuffled") = 0, py::arg("shuffle_seed") = 0,
-      py::arg("stream") = 0);
+      py::arg("stream") = 0, py::arg("sample_table") = 0,
+      py::arg("sample_seed") = 0);
   // the warping gather (csrc/mlp/warp.hip): mlp_affine's arguments, every source position moved by the sample's own
   // displacement field (axes: int32 [h + w][5] on the device; gy, gx: cells per axis; A: the nodes' bound in Q8)
   m.def(
@@ -359,12 +373,14 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       [](uintptr_t X0, uintptr_t labels0, uintptr_t X, uintptr_t labels, uintptr_t XT, uintptr_t Xs, uintptr_t Xw,
          uintptr_t XTw, uintptr_t perm, uintptr_t shifts, uintptr_t transforms, uintptr_t table, int T, int kind,
          uintptr_t axes, int gy, int gx, int A, int N, int Pd, int es, int h, int w, int max_dx, int max_dy,
-         uint32_t aug_seed, uint32_t key, int shuffled, uint32_t shuffle_seed, uintptr_t s) {
+         uint32_t aug_seed, uint32_t key, int shuffled, uint32_t shuffle_seed, uintptr_t s, uintptr_t sample_table,
+         uint32_t sample_seed) {
         cme::WarpArgs wa;
         cme::AffineArgs& fa = wa.aff;
         cme::AugmentArgs& aa = fa.aug;
         aa.base = gather_args(X0, labels0, X, labels, XT, Xs, Xw, XTw, perm, N, Pd, es,
-                              cme::shuffle_key(shuffle_seed, key), shuffled ? 0 : 1);
+                              cme::shuffle_key(shuffle_seed, key), shuffled || sample_table ? 0 : 1, sample_table,
+                              sample_seed, key);
         aa.h = h; aa.w = w; aa.max_dx = max_dx; aa.max_dy = max_dy; aa.akey = cme::augment_key(aug_seed, key);
         aa.shifts = P<int>(shifts);
         fa.table = P<const int32_t>(table); fa.T = T; fa.kind = kind; fa.transforms = P<int>(transforms);
@@ -375,7 +391,8 @@ PYBIND11_MODULE(CME_HIP_MODULE, m) {
       py::arg("XTw"), py::arg("perm"), py::arg("shifts"), py::arg("transforms"), py::arg("table"), py::arg("T"),
       py::arg("kind"), py::arg("axes"), py::arg("gy"), py::arg("gx"), py::arg("A"), py::arg("N"), py::arg("P"),
       py::arg("es"), py::arg("h"), py::arg("w"), py::arg("max_dx"), py::arg("max_dy"), py::arg("aug_seed"),
-      py::arg("key"), py::arg("shuffled") = 0, py::arg("shuffle_seed") = 0, py::arg("stream") = 0);
+      py::arg("key"), py::arg("shuffled") = 0, py::arg("shuffle_seed") = 0, py::arg("stream") = 0,
+      py::arg("sample_table") = 0, py::arg("sample_seed") = 0);
   m.def("mlp_split_fused_tiles", &cme::mlp_split_fused_tiles, py::arg("P"), py::arg("H"), py::arg("cap"));
   // the stateful optimizer step (csrc/mlp/optim.h): kind 0 = momentum / Nesterov, 1 = adam; rec = optim_grid(count)
   // records of 4 doubles {t, b1^t, b2^t, 0}

@@ -17,7 +17,9 @@
 //   X, XT, Xs  from the tile (X with 16-byte LDS reads where VEC).
 // No atomics.  LDS 19 456 B per workgroup (the 17 408 B tile + 2 048 B of row records), 30 VGPRs (1-byte elements) and
 // 32-35 (2 / 4 / 8-byte), 66-68 SGPRs, no scratch, 8 waves per SIMD (the compiler's resource report of the gfx950
-// build).
+// build).  With a sampler's alias table (sample.h) the source row is a keyed draw and the shift and the table entry
+// are keyed by the destination (resident_layouts.h augment_id); with that branch compiled in the report is the same but
+// for the SGPRs: 66-68 before, 70-72 now.
 // Measured (bench/affine_cost.py, docs/PERFORMANCE.md "Affine augmentation"): 60 000 x 784 pixels in 185 us with X, XT
 // and Xs against 73 us for the Shift launch and 44 us for the shuffle launch in the same run (2.55 x the Shift launch),
 // 245 us against 147 us and 112 us with the bf16 copies (1.66 x).  Inside three times the Shift launch, so the staged
@@ -59,8 +61,9 @@ __global__ __launch_bounds__(kThreads) void affine_kernel(AffineArgs fa) {
     i32x4 q{65536, 0, 0, 65536};
     if (d < N) {
       s = source_of(a, d);
-      sh = augment_shift(static_cast<uint32_t>(s), aa.akey, aa.max_dx, aa.max_dy);
-      const int k = static_cast<int>(affine_index(static_cast<uint32_t>(s), aa.akey, static_cast<uint32_t>(fa.T)));
+      const uint32_t id = augment_id(a, d, s);
+      sh = augment_shift(id, aa.akey, aa.max_dx, aa.max_dy);
+      const int k = static_cast<int>(affine_index(id, aa.akey, static_cast<uint32_t>(fa.T)));
       q = *reinterpret_cast<const i32x4*>(fa.table + 4 * k);  // k < T by the reduction
       if (chunk == 0) {
         store_order(a, d, s);

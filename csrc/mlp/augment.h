@@ -3,7 +3,9 @@
 // Once per epoch the augmenting gather rewrites every resident layout from the pristine rows, like the shuffle
 // (shuffle.h), and on the way moves each image by its own (dx, dy).  The rule is stateless and integer-only, so the
 // kernel computes a sample's shift from its SOURCE (loaded) index alone and the host (g++, bindings_cpu.cpp
-// `epoch_shifts` / `augment_rows`) computes the same values from this same header.
+// `epoch_shifts` / `augment_rows`) computes the same values from this same header.  (With a sampler, sample.h, one
+// source row may sit at many places of an epoch: the index hashed is then the DESTINATION's, resident_layouts.h
+// augment_id, here and in affine.h / warp.h.)
 //
 //   * key: augment_key(seed, iter) = shuffle_mix64(shuffle_key(seed, iter) ^ kAugmentStream), `iter` the trainer's
 //     iteration counter at the start of the epoch, exactly as for the shuffle.  The fixed constant (and the mixing)
@@ -58,7 +60,8 @@ __host__ __device__ inline int augment_src_feature(int f, int dx, int dy, int h,
 }
 
 // One launch rewrites every resident layout as mlp_shuffle does (`base`: the same fields with the same meaning;
-// base.identity != 0: no reordering, the shifts still apply -- they are keyed by the source index, which is then i),
+// base.identity != 0: no reordering, the shifts still apply -- they are keyed by the source index, which is then i;
+// base.sample_table != null: the source index is a draw and the shifts are keyed by i),
 // each image moved by augment_shift(source index, akey, max_dx, max_dy) on the way.  shifts: int32 [N][2] = (dx, dy)
 // of RESIDENT sample i (indexed like perm), or null.  `stream` is a hipStream_t.  No sync, no read-back.
 struct AugmentArgs {

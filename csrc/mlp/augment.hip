@@ -13,7 +13,9 @@
 //           of X0 is ever formed and every load is an aligned element load.  Pixels without a source are zeros.
 //   X, XT, Xs  from the tile (X with 16-byte LDS reads where VEC).
 // No atomics.  LDS 18 432 B per workgroup, 14-23 VGPRs, no scratch, 8 waves per SIMD (the compiler's resource report
-// of the gfx950 build).
+// of the gfx950 build).  With a sampler's alias table (sample.h) the source row is a keyed draw and the shift is keyed
+// by the destination (resident_layouts.h augment_id); with that branch compiled in the report is the same but for the
+// SGPRs: 62-66 before, 64-68 now.
 // Measured (bench/augment_cost.py, docs/PERFORMANCE.md "Augmentation"): 60 000 x 784 pixels in 73 us with X, XT and Xs
 // against 44 us for the shuffle launch in the same run (1.66 x), 156 us against 122 us with the bf16 copies (1.28 x).
 // The staged form of the gather (aligned 16-byte loads of the covering span into a second LDS buffer) was not built.
@@ -52,7 +54,7 @@ __global__ __launch_bounds__(kThreads) void augment_kernel(AugmentArgs aa) {
     AugmentShift sh{0, 0};
     if (d < N) {
       s = source_of(a, d);
-      sh = augment_shift(static_cast<uint32_t>(s), aa.akey, aa.max_dx, aa.max_dy);
+      sh = augment_shift(augment_id(a, d, s), aa.akey, aa.max_dx, aa.max_dy);
       if (chunk == 0) {
         store_order(a, d, s);
         if (aa.shifts) {

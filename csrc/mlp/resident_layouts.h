@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "common/hip_common.h"
+#include "sample.h"
 #include "shuffle.h"
 
 namespace cme {
@@ -77,10 +78,21 @@ __device__ __forceinline__ void store1(T* D, uint16_t* Dw, int64_t o, const T v)
 }
 
 // The row prologue of thread d < 64: destination sample d (< N; past N the row is -1) -> its source row, d itself
-// for the identity ...
+// for the identity, a draw with replacement where a sampler's table is given (sample.h), else the keyed permutation.
+// The test of the table pointer is uniform over the launch; against the parent's kernels the table-less shuffle
+// launch measured the same with it (docs/PERFORMANCE.md "Weighted sampling") ...
 __device__ __forceinline__ int source_of(const ShuffleArgs& a, int64_t d) {
-  return a.identity ? static_cast<int>(d)
-                    : static_cast<int>(shuffle_index(static_cast<uint32_t>(d), static_cast<uint32_t>(a.N), a.key));
+  if (a.identity) return static_cast<int>(d);
+  if (a.sample_table)
+    return static_cast<int>(sample_draw(static_cast<uint32_t>(d), static_cast<uint32_t>(a.N), a.sample_key,
+                                        a.sample_table));
+  return static_cast<int>(shuffle_index(static_cast<uint32_t>(d), static_cast<uint32_t>(a.N), a.key));
+}
+// ... the identity the augmentations hash for it: the source row s, so that the order does not change what a sample
+// gets; with a sampler the destination d, since one source row may then sit at many destinations of an epoch and each
+// of them is to get its own shift, table entry and lattice ...
+__device__ __forceinline__ uint32_t augment_id(const ShuffleArgs& a, int64_t d, int s) {
+  return a.sample_table ? static_cast<uint32_t>(d) : static_cast<uint32_t>(s);
 }
 // ... and the chunk-0 workgroup's stores of perm[d] and the gathered label.  (One function that also tested d < N
 // and chunk == 0 made the augment repeat both tests around its shift: + 9 instructions per kernel.)
@@ -165,6 +177,8 @@ inline void check_gather_args(const ShuffleArgs& a, const char* who) {
   CME_REQUIRE(a.X0 != a.X, w + "source and destination must be distinct buffers");
   CME_REQUIRE(a.es == 1 || !(a.Xs || a.Xw || a.XTw), w + "Xs / Xw / XTw derive from uint8 pixels");
   CME_REQUIRE(a.Xs == nullptr || al16(a.Xs), w + "Xs must be 16-byte aligned");
+  CME_REQUIRE((reinterpret_cast<uintptr_t>(a.sample_table) & 7) == 0, w + "the sampler's table must be 8-byte aligned");
+  CME_REQUIRE(a.sample_table != nullptr || a.sample_key == 0, w + "a sampler key needs the sampler's table");
 }
 
 // f(T{}, VEC, VEC_T): T the unsigned integer of `es` bytes, the two forms as std::bool_constant values.  False, and no

@@ -83,6 +83,8 @@ __host__ __device__ inline uint32_t shuffle_index(uint32_t i, uint32_t n, uint64
 // forward's fragment order (mma_tile.h xs_off; es == 1), its zero padding rewritten as zeros; Xw [N][P] and
 // XTw [P (+ 1)][N] the bf16 copies of the wide engines (es == 1; the conversion of 0..255 is exact); perm int32 [N].
 // `stream` is a hipStream_t.  No sync, no read-back.
+// sample_table != null (sample.h: device uint32 [N][2], 8-byte aligned): perm[i] = sample_draw(i, N, sample_key,
+// sample_table) instead -- a draw with replacement, so rows may repeat; identity != 0 still gives perm[i] = i.
 struct ShuffleArgs {
   const void* X0 = nullptr;
   const int* labels0 = nullptr;
@@ -96,6 +98,8 @@ struct ShuffleArgs {
   int N = 0, P = 0, es = 1;
   uint64_t key = 0;
   int identity = 0;
+  const uint32_t* sample_table = nullptr;
+  uint64_t sample_key = 0;
 };
 void mlp_shuffle(const ShuffleArgs& a, void* stream);
 

@@ -9,7 +9,10 @@
 //           16-byte aligned too), 16 rows per pass; else one element per lane.  The same registers go straight to X
 //           (and, converted, to Xw) before the barrier: full rows, coalesced.
 //   XT, Xs  from the tile.
-// LDS 17.3 KB per workgroup, 14-26 VGPRs, no scratch, 8 waves per SIMD.
+//           With a sampler's alias table (sample.h) the source row is a keyed draw with replacement instead: one hash
+//           and one dependent 8-byte load per destination sample, in the same 64 threads.
+// LDS 17.3 KB per workgroup, 14-26 VGPRs, no scratch, 8 waves per SIMD.  With the sampler's branch compiled in the
+// compiler's resource report is unchanged in every form: LDS 17 664 B, 14-26 VGPRs, 52-58 SGPRs, no scratch, 8 waves.
 // Measured (bench/shuffle_cost.py, docs/PERFORMANCE.md "Per-epoch shuffle"): 60 000 x 784 pixels in 38-43 us with X, XT
 // and Xs (1.8 x a copy of the same bytes), 117-122 us with the bf16 copies.  A variant of the XT step that read the
 // tile as four-byte words and transposed 4 x 4 byte blocks in registers (a quarter of the LDS reads) measured the

@@ -27,7 +27,9 @@
 // No atomics.  The compiler's resource report of the gfx950 build: LDS 36 352 B per workgroup (the 17 408 B tile,
 // 2 048 B of row records, 512 B of node keys, 16 384 B of nodes): four workgroups per CU of 160 KiB, so LDS and not
 // the registers bounds the residency at 4 waves per SIMD; 62-64 VGPRs in every form (8 waves per SIMD by registers),
-// 72-76 SGPRs, no scratch.
+// 72-76 SGPRs, no scratch.  With a sampler's alias table (sample.h) the source row is a keyed draw and the shift, the
+// table entry and the lattice are keyed by the destination (resident_layouts.h augment_id); with that branch compiled
+// in the report is the same but for the SGPRs: 74-78.
 // Measured: bench/warp_cost.py, docs/PERFORMANCE.md "Elastic distortion".
 #include "warp.h"
 
@@ -73,10 +75,11 @@ __global__ __launch_bounds__(kThreads) void warp_kernel(WarpArgs wa) {
     uint64_t nk = 0;
     if (d < N) {
       s = source_of(a, d);
-      sh = augment_shift(static_cast<uint32_t>(s), aa.akey, aa.max_dx, aa.max_dy);
-      const int k = static_cast<int>(affine_index(static_cast<uint32_t>(s), aa.akey, static_cast<uint32_t>(fa.T)));
+      const uint32_t id = augment_id(a, d, s);
+      sh = augment_shift(id, aa.akey, aa.max_dx, aa.max_dy);
+      const int k = static_cast<int>(affine_index(id, aa.akey, static_cast<uint32_t>(fa.T)));
       q = *reinterpret_cast<const i32x4*>(fa.table + 4 * k);  // k < T by the reduction
-      nk = warp_node_key(static_cast<uint32_t>(s), aa.akey);
+      nk = warp_node_key(id, aa.akey);
       if (chunk == 0) {
         store_order(a, d, s);
         if (aa.shifts) {
